@@ -6,15 +6,25 @@ drop-in path, grid_kernel.py:56-115 -- lengthscales 0.1*(1+0.05 i), jitter
 1e-12, s = 0.01), all vectors (y, x, r, two p buffers, q, matvec scratch:
 7 x 12.8 GB) resident in HBM.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure
+needs and no more: set-up, W warm-up iterations, the K timed ones, the closing
+update, the result line.  Every other leg below runs only with --full.
+
 Prints ONE JSON line (rank 0):
   metric/value/unit   CG iterations per second, whole job
+  ms_per_step         milliseconds per timed CG iteration
   roofline            the dominant kernel -- the mode-product launch position
                       with the largest share of the timed region, from HIP
                       events recorded by the library on the stream the kernels
                       run on -- against its binding roof (FP64 MFMA or HBM,
                       whichever floor is higher for that launch's algorithmic
                       FLOP and bytes); plus whole-matvec and whole-iteration
-                      fractions
+                      fractions (read off the timed iterations themselves)
+ --full only:
+  prologue_calibration, box
+                      the prologue's streams alone on the solver's buffers
+                      before the iterations; the GPU's clocks, temperatures
+                      and power sampled during the timed iterations
   cpu_baseline        the reference's CPU arithmetic restated
                       (oracle.kron_matvec_dsymm: kron_matrix.py:74-96's dsymm
                       sequence; fidelity vs the reference in
@@ -27,8 +37,19 @@ Prints ONE JSON line (rank 0):
                       the same operator after the CG leg, per-step HIP events
                       recorded by the library (SLQ log-det leg of C3); not
                       part of `value`
+  grief               (--grief C2,C4,C5) one cold GPGriefModel fit per config
+                      (bench_grief.run_config); not part of `value`
+
+--dump-outputs DIR (single GPU): after the timed steps, what a caller of the
+timed path receives once the solve is closed -- DIR/x.npy, the solution vector
+after W + K iterations (float64; above 2^21 entries a fixed, seeded sample of
+that many, their flat indices in DIR/x_index.npy), and DIR/resid.npy, the
+residual norm the solver reports.  The inputs are functions of the arguments
+alone, so two builds run with the same arguments can be compared entry for
+entry.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 200] [--dims 4]
+                  [--dump-outputs DIR] [--full]
 --gpus N > 1 without a launcher: this process starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a child
 (before any GPU call) and exits with its status; under the launcher each rank
@@ -36,6 +57,7 @@ is one GPU (RCCL): strong scaling of the same single CG, factor 0 sharded over
 the ranks.
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -75,17 +97,25 @@ def parse():
     # per matvec); "auto" = the first that applies, in that order
     ap.add_argument("--shard", default="auto", choices=["auto", "block", "parity", "transpose"])
     ap.add_argument("--lanczos", type=int, default=30,
-                    help="also time this many device Lanczos steps (one probe; 0 = off; "
-                         "single GPU only)")
+                    help="with --full: also time this many device Lanczos steps (one probe; "
+                         "0 = off; single GPU only)")
     ap.add_argument("--matvec", type=int, default=5,
-                    help="also time this many isolated K*x matvecs (HIP events per mode "
-                         "product; 0 = off; single GPU only)")
+                    help="with --full: also time this many isolated K*x matvecs (HIP events per "
+                         "mode product; 0 = off; single GPU only)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "push", "a2a"])
     ap.add_argument("--fusion", type=int, default=None, choices=[0, 1, 2],
                     help="fused-CG layout (gg_cg_set_fusion); default: the library's")
     ap.add_argument("--grief", default="C2,C4,C5",
-                    help="P2 GRIEF fits timed after the CG leg (bench_grief configs, "
+                    help="with --full: P2 GRIEF fits timed after the CG leg (bench_grief configs, "
                          "comma-separated; 'off' = none); not part of `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the prologue "
+                         "calibration, the clock sampler, the isolated matvecs, the Lanczos "
+                         "steps, the GRIEF fits and the CPU baseline (--matvec, --lanczos, "
+                         "--grief, --cpu-baseline select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solution of the timed solve (and its residual norm) as "
+                         "DIR/<name>.npy after the timed steps (single GPU)")
     return ap.parse_args()
 
 
@@ -1247,6 +1277,8 @@ class ClockSampler(object):
 # ---------------------------------------------------------------- main
 def main():
     a = parse()
+    if a.dump_outputs and a.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs writes the single-GPU solve (--gpus 1)")
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and a.gpus > 1:
         sys.exit(launch_ranks(a))
@@ -1268,7 +1300,7 @@ def main():
         dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu \
             else torch.device("cpu")
         res = run_sharded(a, world, rank, torch, dev, dist, on_gpu, backend)
-        if on_gpu and a.grief != "off":
+        if a.full and on_gpu and a.grief != "off":
             # P2 beside it: BASELINE C4 is the 4-GPU GRIEF config, C5 the
             # 8-GPU one -- data rows sharded, Gram / Phi^T y all-reduced
             names = {4: ["C4"], 8: ["C5"]}.get(world, [])
@@ -1293,7 +1325,8 @@ def main():
     torch.cuda.synchronize()
     # this box's memory floor for the prologue launch: its six streams alone
     # over the same buffers (gg_cg_calibrate), before any iteration
-    cal_ms, cal_off = solver.calibrate(5)
+    if a.full:
+        cal_ms, cal_off = solver.calibrate(5)
 
     # ---- CG: warmup, then exactly `steps` iterations bracketed by sync.  The
     # recurrence stays open across the two calls (steady state, as inside a
@@ -1307,7 +1340,7 @@ def main():
     # iterations, recorded by the library on the stream the kernels run on
     solver.profile(True)
     torch.cuda.synchronize()
-    clocks = ClockSampler()
+    clocks = ClockSampler() if a.full else contextlib.nullcontext()
     with clocks:
         t0 = time.perf_counter()
         solver.iterate(a.steps, check_every=0, close=False)
@@ -1371,42 +1404,69 @@ def main():
         "closing_ms": closing_ms,
     }
     result.update(extra)
-    # the box: the prologue's streams alone on these
-    # buffers -- the launch's memory floor here -- beside the launch itself
-    rd = bool(getattr(solver, "rderive", False))
-    cal_bytes = (5.0 if rd else 6.0) * 8.0 * n
-    result["prologue_calibration_gbs"] = cal_bytes / (cal_ms * 1e-3) / 1e9
-    result["prologue_calibration"] = {
-        "ms": cal_ms, "bytes": cal_bytes,
-        "pattern": ("read p_old, p_{j-2}, q; write p_new, q (the derived-r prologue's five "
-                    "streams" if rd else
-                    "read p_old, r, q; write r, p_new, q (the fused prologue's six streams") +
-                   ", its non-temporal mask, no MFMA work; gg_cg_calibrate: a plain "
-                   "grid-stride stream kernel, 2 untimed + 5 timed passes -- a reference "
-                   "rate for this box, not a bound)",
-        "buffer_offsets_mod_2MiB": dict(zip(["r" if not rd else "p_{j-2}", "p_old", "p_new",
-                                             "q"], cal_off)),
-        "buffers_256B_aligned": all(v % 256 == 0 for v in cal_off),
-        "prologue_launch_ms": per_pos[0],
-        "prologue_launch_vs_streams": per_pos[0] / cal_ms}
-    result["box"] = clocks.report()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, solver.x, res, torch)
+    if a.full:
+        # the box: the prologue's streams alone on these
+        # buffers -- the launch's memory floor here -- beside the launch itself
+        rd = bool(getattr(solver, "rderive", False))
+        cal_bytes = (5.0 if rd else 6.0) * 8.0 * n
+        result["prologue_calibration_gbs"] = cal_bytes / (cal_ms * 1e-3) / 1e9
+        result["prologue_calibration"] = {
+            "ms": cal_ms, "bytes": cal_bytes,
+            "pattern": ("read p_old, p_{j-2}, q; write p_new, q (the derived-r prologue's five "
+                        "streams" if rd else
+                        "read p_old, r, q; write r, p_new, q (the fused prologue's six streams") +
+                       ", its non-temporal mask, no MFMA work; gg_cg_calibrate: a plain "
+                       "grid-stride stream kernel, 2 untimed + 5 timed passes -- a reference "
+                       "rate for this box, not a bound)",
+            "buffer_offsets_mod_2MiB": dict(zip(["r" if not rd else "p_{j-2}", "p_old", "p_new",
+                                                 "q"], cal_off)),
+            "buffers_256B_aligned": all(v % 256 == 0 for v in cal_off),
+            "prologue_launch_ms": per_pos[0],
+            "prologue_launch_vs_streams": per_pos[0] / cal_ms}
+        result["box"] = clocks.report()
     del solver, y
-    torch.cuda.empty_cache()
-    if a.matvec > 0:
-        result["matvec"] = time_matvec(K, n, m, d, fold_mask, torch, dev, a.matvec)
+    if a.full:
         torch.cuda.empty_cache()
-        if K._device().block_info()[0]:
-            result["block_matvec"] = time_block_matvec(K, n, m, d, torch, dev, a.matvec)
+        if a.matvec > 0:
+            result["matvec"] = time_matvec(K, n, m, d, fold_mask, torch, dev, a.matvec)
             torch.cuda.empty_cache()
-    if a.lanczos > 0:
-        result["lanczos"] = time_lanczos(K, s, a.lanczos, torch, n, m, d, fold_mask)
-        torch.cuda.empty_cache()
-    if a.grief != "off":
-        result["grief"] = grief_leg([c.strip() for c in a.grief.split(",") if c.strip()], torch,
-                                    a.cpu_baseline == "auto")
-    if a.cpu_baseline == "auto":
-        result["cpu_baseline"] = cpu_baseline(F, s, a.cpu_iters)
+            if K._device().block_info()[0]:
+                result["block_matvec"] = time_block_matvec(K, n, m, d, torch, dev, a.matvec)
+                torch.cuda.empty_cache()
+        if a.lanczos > 0:
+            result["lanczos"] = time_lanczos(K, s, a.lanczos, torch, n, m, d, fold_mask)
+            torch.cuda.empty_cache()
+        if a.grief != "off":
+            result["grief"] = grief_leg([c.strip() for c in a.grief.split(",") if c.strip()],
+                                        torch, a.cpu_baseline == "auto")
+        if a.cpu_baseline == "auto":
+            result["cpu_baseline"] = cpu_baseline(F, s, a.cpu_iters)
     print(json.dumps(result), flush=True)
+
+
+DUMP_SAMPLE = 1 << 21   # entries of x written by --dump-outputs (16 MB + their indices)
+DUMP_SEED = 0
+
+
+def dump_outputs(path, x, resid, torch):
+    """--dump-outputs: the closed solve's solution x (what KronCG.x holds for
+    its caller) and the residual norm of gg_cg_status, as float64 .npy files.
+    Above DUMP_SAMPLE entries x is sampled at fixed flat indices (seeded,
+    sorted, drawn with replacement), written beside it as x_index.npy -- exact
+    in float64 below 2^53."""
+    os.makedirs(path, exist_ok=True)
+    flat = x.reshape(-1)
+    n = flat.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    else:
+        idx = np.arange(n)
+    np.save(os.path.join(path, "x.npy"), flat.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "x_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "resid.npy"), np.array([resid], dtype=np.float64))
 
 
 if __name__ == "__main__":

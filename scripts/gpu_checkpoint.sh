@@ -1,7 +1,8 @@
 #!/bin/bash
 # Checkpoint on one MI355X: the whole GPU suite, smoke(), the PMC traffic of
-# the CG mode products (taken first, so the bench reports it), the default
-# bench (with its CPU baseline and GRIEF leg) and a kernel-trace profile of it.
+# the CG mode products (taken first, so the bench reports it), the full
+# bench (--full: with its CPU baseline and GRIEF leg) and a kernel-trace
+# profile of it.
 set -o pipefail
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
@@ -22,7 +23,7 @@ timeout -s KILL 240 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --ke
 python3 tools/pmc_traffic.py $O/mp_rd $O/mp_wr $O/pmc_mode_product.json
 # the bench below reports these counters when they match its kernels
 mkdir -p profiles/r04 && cp $O/pmc_mode_product.json profiles/r04/pmc_mode_product.json
-timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['ms_per_step'], [round(v,2) for v in d['mode_product_ms_by_position']], d['roofline']['frac'], d['roofline']['traffic'], d['cpu_baseline']['value'], d['lanczos']['ms_per_step'], {k: round(v['fit_ms'],2) for k, v in d['grief'].items()})"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o run -- python3 -u bench.py --steps 10 --warmup 2 --cpu-baseline off --lanczos 0 --grief off > $O/bench_prof.json 2> $O/bench_prof.err || { tail -5 $O/bench_prof.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o run -- python3 -u bench.py --full --steps 10 --warmup 2 --cpu-baseline off --lanczos 0 --grief off > $O/bench_prof.json 2> $O/bench_prof.err || { tail -5 $O/bench_prof.err; exit 1; }
 echo checkpoint done
