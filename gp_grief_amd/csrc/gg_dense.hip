@@ -1425,6 +1425,10 @@ int gg_gemm(int trans_a, int trans_b, int M, int N, int K, double alpha, const d
     GG_REQUIRE(M >= 0 && N >= 0 && K >= 0, GG_ERR_VALUE, "negative dimension");
     GG_REQUIRE(C_dev && (K == 0 || (A_dev && B_dev)), GG_ERR_VALUE, "NULL matrix");
     GG_REQUIRE(uplo >= 0 && uplo <= 2, GG_ERR_VALUE, "bad uplo");
+    // leading dimensions cover the stored row (the header's ld rule)
+    GG_REQUIRE(ldc >= N, GG_ERR_VALUE, "ldc below the columns of C");
+    GG_REQUIRE(K == 0 || (lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N)), GG_ERR_VALUE,
+               "lda / ldb below the columns of the stored operand");
     gg::gemm(trans_a != 0, trans_b != 0, M, N, K, alpha, A_dev, lda, B_dev, ldb, beta, C_dev,
              ldc, uplo, gg::as_stream(stream), splitk_dev, splitk_elems);
   });
@@ -1435,6 +1439,7 @@ int gg_gemv(int trans, int64_t rows, int cols, double alpha, const double* A_dev
             int64_t work_elems, gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(rows >= 0 && cols >= 0 && A_dev && x_dev && y_dev, GG_ERR_VALUE, "bad argument");
+    GG_REQUIRE(lda >= cols, GG_ERR_VALUE, "lda below the columns of A");
     gg::gemv(trans != 0, rows, cols, alpha, A_dev, lda, x_dev, beta, y_dev, work_dev,
              work_elems, gg::as_stream(stream));
   });
@@ -1444,6 +1449,7 @@ int gg_add_diag(int n, const double* A_dev, int64_t lda, double s, const double*
                 double* P_dev, int64_t ldp, gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(n >= 0 && A_dev && P_dev, GG_ERR_VALUE, "bad argument");
+    GG_REQUIRE(lda >= n && ldp >= n, GG_ERR_VALUE, "lda / ldp below n");
     if (n == 0) return;
     const int nb = (int)std::min<int64_t>(4096, gg::ceil_div((int64_t)n * n, 256));
     hipLaunchKernelGGL(gg::add_diag_kernel, dim3(nb), dim3(256), 0, gg::as_stream(stream), n,
@@ -1465,6 +1471,7 @@ int gg_potrf(int n, double* A_dev, int64_t lda, double* winv_dev, double* logdet
              gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(n >= 1 && A_dev && winv_dev, GG_ERR_VALUE, "bad argument");
+    GG_REQUIRE(lda >= n, GG_ERR_VALUE, "lda below n");
     hipStream_t s = gg::as_stream(stream);
     const int nblk = (int)gg::ceil_div(n, gg::kNB);
     int* status = reinterpret_cast<int*>(winv_dev + (int64_t)nblk * gg::kNB * gg::kNB);
@@ -1646,6 +1653,7 @@ int gg_potrs(int n, int r, const double* L_dev, int64_t lda, const double* winv_
                "bad argument");
     GG_REQUIRE(!((which & 4) && (which & 2)), GG_ERR_VALUE,
                "triangular right-hand side is forward-only");
+    GG_REQUIRE(lda >= n && ldb >= r, GG_ERR_VALUE, "lda below n or ldb below r");
     if (r == 0) return;
     hipStream_t s = gg::as_stream(stream);
     const int nblk = (int)gg::ceil_div(n, gg::kNB);
@@ -1804,6 +1812,7 @@ int gg_colsumsq_lower(int n, const double* M_dev, int64_t ld, double* out_dev,
                       gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(n >= 0 && M_dev && out_dev, GG_ERR_VALUE, "bad argument");
+    GG_REQUIRE(ld >= n, GG_ERR_VALUE, "ld below n");
     if (n == 0) return;
     hipLaunchKernelGGL(gg::colsumsq_kernel, dim3((unsigned)gg::ceil_div(n, 64)), dim3(1024), 0,
                        gg::as_stream(stream), n, M_dev, ld, out_dev);

@@ -280,8 +280,17 @@ __device__ void tq_bisect(const double* __restrict__ d, const double* __restrict
     red[1] = hi + 2.1 * 2.220446049250313e-16 * nrm * m + 1e-300;
     red[2] = fmax(2.2250738585072014e-308, 2.2250738585072014e-308 * emax);   // pivmin
     red[3] = 4.0 * 2.220446049250313e-16 * fmax(nrm, 1e-300);                 // width
+    // a one-point Gershgorin interval (T = c I, the zero matrix included)
+    // holds every eigenvalue exactly; bisecting the widened bracket would
+    // return c -+ pivmin instead
+    red[4] = lo == hi ? 1.0 : 0.0;
+    red[5] = lo;
   }
   __syncthreads();
+  if (red[4] != 0.0) {
+    for (int i = tid; i < m; i += nt) lam[i] = red[5];
+    return;
+  }
   const double glo = red[0], ghi = red[1], pivmin = red[2], width = red[3];
   int G = 1;
   while (G < 8 && 2 * G * m <= nt) G *= 2;
@@ -558,7 +567,12 @@ __global__ __launch_bounds__(kTqThreads) void tridiag_ql_kernel(
   // Wave 0's loop state is wave-uniform (readfirstlane): its branches are
   // scalar, and every lane runs the chain's arithmetic in lockstep.
   const int wv = __builtin_amdgcn_readfirstlane(wave);
-  int l = 0, iter = 0;   // wave-0 state
+  // The sweep budget is for the whole matrix, max_iter * m (LAPACK dsteqr's
+  // 30 n), not per eigenvalue: the first eigenvalue of a large cluster -- the
+  // ~1e-12 tail of an RBF factor, m = 512 -- takes over a hundred sweeps
+  // before the first deflation and the rest about two each.
+  int l = 0, iter = 0;   // wave-0 state; iter: sweeps so far
+  const int64_t budget = (int64_t)max_iter * m;
   int kswp = 0;
   for (int k = 0;; ++k) {
     kswp = k;
@@ -581,7 +595,6 @@ __global__ __launch_bounds__(kTqThreads) void tridiag_ql_kernel(
         mm = __builtin_amdgcn_readfirstlane(mm);
         if (mm == l) {   // d[l] converged
           ++l;
-          iter = 0;
           continue;
         }
         have = true;
@@ -593,7 +606,7 @@ __global__ __launch_bounds__(kTqThreads) void tridiag_ql_kernel(
           lo_b[b] = hi_b[b] = 0;
           ql_done = 1;
         }
-      } else if (iter >= max_iter) {
+      } else if (iter >= budget) {
         if (lane == 0) {
           bad = 1;
           lo_b[b] = hi_b[b] = 0;

@@ -68,6 +68,19 @@ __global__ __launch_bounds__(kVecThreads) void dot_partials_kernel(const double*
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
+// The same partial sums one double at a time: gg_dot on a vector that does not
+// start on a 16-byte boundary (a view one double into an allocation).
+__global__ __launch_bounds__(kVecThreads) void dot_partials_unaligned_kernel(
+    const double* __restrict__ x, const double* __restrict__ y, int64_t n,
+    double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    acc = fma(x[i], y[i], acc);
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 __global__ __launch_bounds__(1024) void reduce_kernel(const double* __restrict__ partials,
                                                       int64_t count, double* __restrict__ out) {
   double acc = 0.0;
@@ -96,9 +109,10 @@ static int vec_blocks(int64_t n) {
   return (int)std::min<int64_t>(kVecBlocks, std::max<int64_t>(want, 1));
 }
 
-__global__ __launch_bounds__(kVecThreads) void axpby_kernel(double a, const double* __restrict__ x,
-                                                            double b, double* __restrict__ y,
-                                                            int64_t n) {
+// x may be y itself (the models scale a vector in place: axpby(0, v, s, v)),
+// so neither pointer is __restrict__
+__global__ __launch_bounds__(kVecThreads) void axpby_kernel(double a, const double* x, double b,
+                                                            double* y, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     y[i] = a * x[i] + b * y[i];
@@ -1021,7 +1035,13 @@ int gg_dot(const double* x_dev, const double* y_dev, int64_t n, double* out_host
     double* buf = nullptr;
     GG_HIP(hipMallocAsync(&buf, (gg::kVecBlocks + 1) * sizeof(double), s));
     const int nb = gg::vec_blocks(n);
-    gg::launch_dot_partials(x_dev, y_dev, n, buf, nb, s);
+    if (gg::aligned16(x_dev) && gg::aligned16(y_dev)) {
+      gg::launch_dot_partials(x_dev, y_dev, n, buf, nb, s);
+    } else {
+      hipLaunchKernelGGL(gg::dot_partials_unaligned_kernel, dim3(nb), dim3(gg::kVecThreads), 0,
+                         s, x_dev, y_dev, n, buf);
+      GG_LAUNCH_CHECK();
+    }
     gg::launch_reduce_to(buf, nb, buf + gg::kVecBlocks, s);
     GG_HIP(hipMemcpyAsync(out_host, buf + gg::kVecBlocks, sizeof(double),
                           hipMemcpyDeviceToHost, s));

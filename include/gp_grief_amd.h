@@ -151,10 +151,13 @@ int gg_kron_logdet_shifted(int d, const int64_t* m, const double* lam_dev, doubl
                            double* out_host, gg_stream stream);
 
 /* ------------------------------------------------- vector primitives (CG ops) */
+/* x . y (0 for n = 0); x and y at any 8-byte aligned address; synchronising. */
 int gg_dot(const double* x_dev, const double* y_dev, int64_t n, double* out_host,
-           gg_stream stream); /* synchronising */
+           gg_stream stream);
+/* y = a x + b y.  x_dev may equal y_dev (y = (a + b) y, e.g. the in-place
+ * scaling axpby(0, v, s, v)); partially overlapping x and y are not allowed. */
 int gg_axpby(double a, const double* x_dev, double b, double* y_dev, int64_t n,
-             gg_stream stream); /* y = a x + b y */
+             gg_stream stream);
 /* A[i][:] *= w[i] (mode 0), /= w[i] (mode 1), or A = A*A elementwise (mode 2). */
 int gg_scale_rows(double* A_dev, int64_t rows, int64_t cols, const double* w_dev, int mode,
                   gg_stream stream);
@@ -355,7 +358,11 @@ int gg_probe_fill(uint64_t seed, int probe, double* z_dev, int64_t n, gg_stream 
  * Householder tridiagonalisation + implicit QL on device, one workgroup per
  * matrix (GG_EIG=jacobi: parallel cyclic Jacobi).  A_dev: `count` row-major
  * m[i] x m[i] symmetric matrices concatenated; on return Q_dev holds the
- * eigenvectors (columns) and lam_dev the eigenvalues, ascending.              */
+ * eigenvectors (columns) and lam_dev the eigenvalues, ascending.  1 <= m[i] <=
+ * 2048 (else GG_ERR_VALUE); the factors of one call may differ in size.  QL
+ * takes at most max(30, max_sweeps) * m[i] sweeps over a matrix as a whole
+ * (the budget of LAPACK's dsteqr; Jacobi: max_sweeps cycles), else
+ * GG_ERR_LINALG.                                                             */
 int gg_sym_eig_batched(int count, const int64_t* m, const double* A_dev, double* Q_dev,
                        double* lam_dev, double* work_dev, int64_t work_elems,
                        int max_sweeps, gg_stream stream);
@@ -440,6 +447,18 @@ int gg_expand_skc(const double* x_dev, int U, int64_t n, const int* cidx_dev, in
                   int logged, double* out_dev, int* sign_dev, gg_stream stream);
 
 /* ----------------------------------------- dense FP64 (GRIEF p x p system)
+ * Leading dimensions (lda, ldb, ldc, ldp, ldx, ld), one rule for every entry
+ * point of this section: a matrix is row-major, element (i, j) at
+ * ptr[i * ld + j], and ld must be at least the number of columns of the matrix
+ * as stored (for gg_gemm: A is M x K, or K x M when trans_a; B is K x N, or
+ * N x K when trans_b; C is M x N; for the n x n operands ld >= n; for
+ * gg_potrs's B ldb >= r).  A smaller ld is GG_ERR_VALUE, raised before any
+ * device work.  The ld - cols padding doubles of every row are never read
+ * into a result and never written, so a matrix may be a view into a wider
+ * allocation; it may start at any 8-byte aligned address (which kernel runs
+ * may depend on alignment and on the parity of ld, the result's accuracy does
+ * not).
+ *
  * C = alpha op(A) op(B) + beta C on FP64 MFMA, row-major with leading dims.
  * uplo 1/2 writes only the lower/upper triangle.  splitk_dev (optional,
  * splitk_elems doubles) enables split-K for tall-skinny products such as
@@ -466,6 +485,8 @@ int gg_add_diag(int n, const double* A_dev, int64_t lda, double s, const double*
 /* Blocked Cholesky P = L L^T in place (lower), cho_factor, :153.  winv_dev
  * (gg_potrf_work_elems) receives the inverted diagonal blocks used by
  * gg_potrs; logdet_host = log det P.  Non-SPD -> GG_ERR_LINALG (synchronising).
+ * Only the lower triangle (diagonal included) of A is overwritten, with L; the
+ * strict upper triangle is never written and keeps the caller's values.
  * The trailing updates run on a second stream of the device (look-ahead);
  * the call returns with all of its work complete. */
 int gg_potrf_work_elems(int n, int64_t* elems);
