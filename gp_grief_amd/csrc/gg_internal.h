@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -219,6 +220,35 @@ struct OutMap {
 // Reduction partial-buffer length used by grid-stride vector kernels.
 constexpr int kVecBlocks = 2048;
 constexpr int kVecThreads = 256;
+
+// blocks of a grid-stride vector kernel over n / 2 double2 lanes
+inline int vec_blocks(int64_t n) {
+  const int64_t want = ceil_div(std::max<int64_t>(n / 2, 1), kVecThreads);
+  return (int)std::min<int64_t>(kVecBlocks, std::max<int64_t>(want, 1));
+}
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// block (<= 1024 threads) sum; result valid in thread 0
+__device__ __forceinline__ double block_sum(double v) {
+  __shared__ double red[16];
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+    const int nw = (blockDim.x + 63) >> 6;
+    for (int i = 0; i < nw; ++i) s += red[i];
+  }
+  return s;
+}
+#endif
 
 // ---- the sharded CG's scalar state (gg_vec.hip gg_cgs), for the fused
 // sharded phase 1 in gg_kron.hip ----

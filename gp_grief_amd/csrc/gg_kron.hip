@@ -1075,6 +1075,13 @@ bool kron_first_single_launch(const gg_kron* K) { return K->fwd[0].JT <= kMaxJT;
 int64_t kron_n(const gg_kron* K) { return K->n_rows; }
 const BlockOp* kron_block(const gg_kron* K) { return K->blk; }
 int kron_d(const gg_kron* K) { return K->d; }
+// rows / cols of every factor, in the operator's factor order (d entries each)
+void kron_factor_shape(const gg_kron* K, int64_t* rows, int64_t* cols) {
+  for (int k = 0; k < K->d; ++k) {
+    rows[k] = K->fwd[k].p;
+    cols[k] = K->fwd[k].q;
+  }
+}
 // x_defer mode 2: the side jobs' half boundary of an n-vector (d >= 4: two
 // launches per half, quarters of 2 ceil(n / 8) elements; else one launch per
 // half of 2 ceil(n / 4)); the closing flush uses the same boundary

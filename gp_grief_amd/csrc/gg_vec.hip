@@ -28,26 +28,7 @@ bool kron_first_single_launch(const gg_kron* K);
 int64_t kron_side_half(const gg_kron* K, int64_t n);
 const BlockOp* kron_block(const gg_kron* K);
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// block (<= 1024 threads) sum; result valid in thread 0
-__device__ __forceinline__ double block_sum(double v) {
-  __shared__ double red[16];
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int i = 0; i < nw; ++i) s += red[i];
-  }
-  return s;
-}
+// wave_sum / block_sum / vec_blocks: gg_internal.h (shared with gg_cgm.hip)
 
 __global__ __launch_bounds__(kVecThreads) void dot_partials_kernel(const double* __restrict__ x,
                                                                    const double* __restrict__ y,
@@ -102,11 +83,6 @@ void launch_dot_partials(const double* x, const double* y, int64_t n, double* pa
 void launch_reduce_to(const double* partials, int64_t count, double* out, hipStream_t s) {
   hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(1024), 0, s, partials, count, out);
   GG_LAUNCH_CHECK();
-}
-
-static int vec_blocks(int64_t n) {
-  const int64_t want = ceil_div(std::max<int64_t>(n / 2, 1), kVecThreads);
-  return (int)std::min<int64_t>(kVecBlocks, std::max<int64_t>(want, 1));
 }
 
 // x may be y itself (the models scale a vector in place: axpby(0, v, s, v)),

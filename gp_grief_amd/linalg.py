@@ -9,6 +9,9 @@ Host utilities with the reference's behaviour (gp_grief/linalg.py):
 Device solvers (no reference implementation exists):
   cg            -- scipy.sparse.linalg.cg's recurrence on (K + shift I), every
                    vector op and scalar on the MI355X (gg_cg_*).
+  MaskedKronCG  -- the same CG on (W K W + shift I) x = W b, W = diag(mask): the
+                   grid with missing observations (gg_cgm_*; cg(mask=...)),
+                   optionally preconditioned by the Kronecker eigenpairs.
   slq_logdet    -- stochastic Lanczos quadrature, Lanczos on the device
                    (gg_lanczos_probe); the k x k tridiagonal eigensolve of the
                    quadrature is host-side (k <= a few hundred).
@@ -261,12 +264,118 @@ class KronCG(object):
             pass
 
 
+def _mask_to_device(mask, n):
+    """(uint8 device tensor of n entries, observed count) from a bool / uint8
+    mask, numpy or device; nonzero = observed."""
+    from . import device as dev
+    t = dev.torch()
+    if isinstance(mask, t.Tensor):
+        m = mask.detach().reshape(-1)
+    else:
+        m = t.from_numpy(np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0))
+    if m.numel() != n:
+        raise ValueError("mask must have %d entries, not %d" % (n, m.numel()))
+    m = (m != 0).to(device=dev.device(), dtype=t.uint8).contiguous()
+    n_obs = int(m.sum().item())
+    if n_obs == 0:
+        raise ValueError("mask has no observed point")
+    return m, n_obs
+
+
+class MaskedKronCG(object):
+    """Resident CG state for (W K W + shift I) x = W b, W = diag(mask), on one
+    MI355X (gg_cgm_*): the grid GP with missing observations.  x is zero at the
+    missing points and solves (K_oo + shift I) x_o = b_o on the observed ones;
+    b at the missing points is ignored (it may be NaN).  Runs in the grid basis
+    (W is not diagonal in the parity-block basis) with the textbook
+    recurrence; start / iterate / status as KronCG.
+
+    precond='kron': z = W Q diag(1 / (lam + shift)) Q^T r from the per-factor
+    eigenpairs K.schur() -- the exact inverse on the full grid, two more Kron
+    matvecs per iteration (fewer iterations at low missing fractions).
+    """
+
+    def __init__(self, K, shift, mask, precond=None):
+        from . import device as dev
+        from . import native
+        if precond not in (None, 'kron'):
+            raise ValueError("precond must be None or 'kron'")
+        self.K = K
+        self.shift = float(shift)
+        self.n = int(K.shape[0])
+        self.mask, self.n_observed = _mask_to_device(mask, self.n)
+        self._dk = K._device()
+        L = native.lib()
+        we = ctypes.c_int64()
+        native.check(L.gg_cgm_work_elems(self._dk.h, ctypes.byref(we)), "gg_cgm_work_elems")
+        self.work = dev.empty(we.value)
+        h = ctypes.c_void_p()
+        native.check(L.gg_cgm_create(self._dk.h, self.shift,
+                                     ctypes.c_void_p(self.mask.data_ptr()),
+                                     native.dptr(self.work), ctypes.byref(h)), "gg_cgm_create")
+        self.h = h
+        self.precond = precond
+        if precond == 'kron':
+            Q, T = K.schur()
+            lam = [np.asarray(e, dtype=np.float64).reshape(-1) for e in T.diag().K]
+            self._Q, self._qd = Q, Q._device()
+            self._lam = dev.to_device(np.concatenate(lam))
+            native.check(L.gg_cgm_set_precond(h, self._qd.h, native.dptr(self._lam)),
+                         "gg_cgm_set_precond")
+        self.x = None
+
+    def start(self, b_dev, rtol=1e-5, atol=0.0, x_out=None):
+        from . import device as dev
+        from . import native
+        if b_dev.numel() != self.n:
+            raise ValueError("b must have %d entries" % self.n)
+        self.b = b_dev.reshape(-1)
+        self.x = dev.empty(self.n) if x_out is None else x_out
+        native.check(native.lib().gg_cgm_start(self.h, native.dptr(self.b), native.dptr(self.x),
+                                               float(rtol), float(atol), native.stream_ptr()),
+                     "gg_cgm_start")
+
+    def iterate(self, n_iter, check_every=0):
+        from . import native
+        n_iter = min(int(n_iter), 2 ** 31 - 1)
+        native.check(native.lib().gg_cgm_iterate(self.h, n_iter, min(int(check_every), n_iter),
+                                                 native.stream_ptr()), "gg_cgm_iterate")
+
+    def status(self):
+        from . import native
+        it, conv = ctypes.c_int(), ctypes.c_int()
+        res, tol = ctypes.c_double(), ctypes.c_double()
+        native.check(native.lib().gg_cgm_status(self.h, ctypes.byref(it), ctypes.byref(conv),
+                                                ctypes.byref(res), ctypes.byref(tol),
+                                                native.stream_ptr()), "gg_cgm_status")
+        return it.value, bool(conv.value), res.value, tol.value
+
+    def solve(self, b_dev, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, x_out=None):
+        """start + iterate to convergence: (x, iterations, converged, |r|, tol)."""
+        if maxiter is None:
+            maxiter = self.n * 10
+        if check_every is None:
+            check_every = 10 if self.n >= 1 << 20 else 50
+        self.start(b_dev, rtol, atol, x_out=x_out)
+        self.iterate(maxiter, check_every=check_every)
+        return (self.x,) + self.status()
+
+    def __del__(self):
+        try:
+            from . import native
+            if getattr(self, "h", None) is not None and self.h.value:
+                native.load().gg_cgm_destroy(self.h)
+        except Exception:
+            pass
+
+
 def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, callback=None,
-       recurrence="fused", fusion=None, basis=None, comm=None, decomposition="auto"):
+       recurrence=None, fusion=None, basis=None, comm=None, decomposition="auto",
+       mask=None, precond=None):
     """Solve (K + shift I) x = b with CG on the device (x0 = 0).
 
     Same stopping rule and iterates as scipy.sparse.linalg.cg (recurrence:
-    see KronCG).  b: numpy
+    see KronCG; None = "fused", or "textbook" with mask=).  b: numpy
     (N,1)/(N,) or a CUDA tensor; x is returned in the same kind.  `callback`
     (e.g. a solver_counter) is called once per completed iteration, after the
     solve, with no arguments beyond the counter protocol (the iterates stay on
@@ -279,9 +388,32 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
     distributed.solve (decomposition "auto": the parity-block basis's blocks
     over 2^K ranks where it exists, else the even / odd parity blocks, else
     factor 0 sharded).
+
+    mask (bool / uint8, N entries, numpy or device; nonzero = observed): the
+    grid with missing observations -- CG on (W K W + shift I) x = W b, W =
+    diag(mask) (MaskedKronCG): x is 0 at the missing points and (K_oo + shift
+    I)^-1 b_o on the observed ones, b there is ignored (NaN allowed).  Grid
+    basis, textbook recurrence, one GPU: mask cannot be combined with comm=,
+    basis='block' or an explicit recurrence='fused'.  precond='kron' (needs
+    mask): the Kronecker eigenpair preconditioner of MaskedKronCG.
     """
     from . import device as dev
     n = int(K.shape[0])
+    if precond is not None and mask is None:
+        raise ValueError("precond= needs mask= (on a complete grid solve_schur is exact)")
+    if mask is not None:
+        if comm is not None:
+            raise ValueError("mask=: the masked CG runs on one GPU, comm= cannot be combined")
+        if basis == "block":
+            raise ValueError("mask=: W is not diagonal in the parity-block basis; use "
+                             "basis='grid' (or None)")
+        if recurrence not in (None, "textbook"):
+            raise ValueError("mask=: the masked CG runs the textbook recurrence; "
+                             "recurrence='fused' cannot be combined")
+        if fusion is not None:
+            raise ValueError("mask=: the masked CG has no fusion layouts")
+        if precond not in (None, 'kron'):
+            raise ValueError("precond must be None or 'kron'")
     was_dev = dev.is_device_array(b)
     bd = dev.to_device(b)
     if bd.numel() != n:
@@ -290,6 +422,8 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
         maxiter = n * 10
     if check_every is None:
         check_every = 10 if n >= 1 << 20 else 50
+    if recurrence is None and mask is None:
+        recurrence = "fused"
     if comm is not None:
         from . import distributed
         # the sharded solve runs its own recurrence (fused, layout 0, in the
@@ -308,6 +442,22 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
         res, tol = getattr(distributed.solve, "last_resid", (None, None))
         cg.last = CGResult(out, info, it, res, tol)
         cg.last.decomposition = how
+        return out, info
+    if mask is not None:
+        solver = MaskedKronCG(K, shift, mask, precond=precond)
+        solver.start(bd, rtol, atol)
+        solver.iterate(maxiter, check_every=check_every)
+        it, conv, res, tol = solver.status()
+        if callback is not None:
+            for _ in range(it):
+                callback()
+        info = 0 if conv else it
+        x = solver.x
+        if was_dev:
+            out = x.reshape(tuple(b.shape)) if b.numel() == n else x
+        else:
+            out = dev.to_host(x).reshape(np.shape(b))
+        cg.last = CGResult(out, info, it, res, tol)
         return out, info
     solver = KronCG(K, shift, recurrence, fusion=fusion, basis=basis)
     solver.start(bd, rtol, atol)

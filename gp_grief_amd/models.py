@@ -15,7 +15,10 @@
   GPGridModel    (new, the north star's P1 model) exact or CG grid GP on a full
                  Kronecker-structured grid: KronMatrix operator, device CG /
                  exact eigen-solve, exact or Lanczos (SLQ) log det, posterior
-                 mean and latent variance on the grid.
+                 mean and latent variance on the grid.  With mask= the grid is
+                 incomplete: masked device CG (linalg.MaskedKronCG), exact
+                 (Schur identity) or scaled-eigenvalue log det, imputed grid
+                 mean, off-grid mean and variance.
 
 Device state keeps the reference's attribute names (_Phi, _A, _P, _Pchol,
 _alpha, _alpha_p) holding CUDA tensors (or small host arrays where the
@@ -677,22 +680,52 @@ class GPGridModel(BaseModel):
     posterior mean K alpha and latent variance (Q o Q)-Kron (t s / (t + s)).
 
     solver: 'exact' (per-factor eigendecomposition, two device Kron matvecs
-    and a decoded divide) or 'cg' (device CG, linalg.KronCG).  logdet: 'exact'
+    and a decoded divide; the default on a complete grid) or 'cg' (device CG,
+    linalg.KronCG; the default, and the only choice, with mask=).  logdet: 'exact'
     (streamed over the grid on the device) or 'slq'.  Y (N,1) numpy or CUDA
     tensor; results come back in the same kind.  grad_method is finite
     differences over (noise, kernel parameters) like the reference's
     kernel-parameter path.
+
+    mask (bool / uint8, N entries, numpy or device; nonzero = observed): the
+    grid with missing observations.  Y at the missing points is ignored (NaN
+    allowed).  The Kronecker eigendecomposition no longer diagonalises the
+    system, so the solve is the masked CG (linalg.MaskedKronCG; solver='cg',
+    precond None or 'kron'), alpha is 0 at the missing points, and the LML is
+    -1/2 (y_o^T alpha_o + log det(K_oo + s I) + n log 2 pi) over the n observed
+    points.  logdet: 'exact' -- the Schur identity sum_N log(lam_g + s) +
+    log det[((K + s I)^-1)_mm] with the m x m block from m exact solves of unit
+    vectors and a device Cholesky, for m <= exact_missing_max (a cost guard on
+    m Kronecker matvecs and an m x m Cholesky, not a tuned value); or
+    'scaled_eigs' -- Wilson's approximation sum_{i <= n} log((n / N) lam_(i) + s)
+    over the n largest Kronecker eigenvalues.
     """
 
-    def __init__(self, xg, Y, kern, noise_var=1., solver='exact', logdet='exact',
-                 dim_noise_var=1e-12, cg_rtol=1e-10, slq_probes=8, slq_steps=50, seed=0):
+    def __init__(self, xg, Y, kern, noise_var=1., solver=None, logdet='exact',
+                 dim_noise_var=1e-12, cg_rtol=1e-10, slq_probes=8, slq_steps=50, seed=0,
+                 mask=None, precond=None, exact_missing_max=1024):
         super(GPGridModel, self).__init__()
         from .kern import GridKernel
         assert isinstance(kern, GridKernel)
+        if solver is None:
+            solver = 'exact' if mask is None else 'cg'
         if solver not in ('exact', 'cg'):
             raise ValueError("solver must be 'exact' or 'cg'")
-        if logdet not in ('exact', 'slq'):
-            raise ValueError("logdet must be 'exact' or 'slq'")
+        if mask is None:
+            if logdet not in ('exact', 'slq'):
+                raise ValueError("logdet must be 'exact' or 'slq'")
+            if precond is not None:
+                raise ValueError("precond= needs mask= (a complete grid is solved exactly)")
+        else:
+            if solver == 'exact':
+                raise ValueError("mask=: solver='exact' does not apply to an incomplete grid "
+                                 "(the eigendecomposition no longer diagonalises it); "
+                                 "use solver='cg'")
+            if logdet not in ('exact', 'scaled_eigs'):
+                raise ValueError("mask=: logdet must be 'exact' (Schur identity) or "
+                                 "'scaled_eigs', not %r" % (logdet,))
+            if precond not in (None, 'kron'):
+                raise ValueError("precond must be None or 'kron'")
         self.xg = xg
         self.kern = kern
         self.num_data = int(np.prod([np.shape(g)[0] for g in xg]))
@@ -705,6 +738,16 @@ class GPGridModel(BaseModel):
         self.dim_noise_var = float(dim_noise_var)
         self.cg_rtol = float(cg_rtol)
         self.slq = (int(slq_probes), int(slq_steps), int(seed))
+        self.precond = precond
+        self.exact_missing_max = int(exact_missing_max)
+        self._mask = self._mcg = self._mcg_key = None
+        self.num_observed = self.num_data
+        if mask is not None:
+            from .linalg import _mask_to_device
+            self._mask, self.num_observed = _mask_to_device(mask, self.num_data)
+            # Y at the missing points is never read again (it may be NaN)
+            t = dev.torch()
+            self._yd = t.where(self._mask != 0, self._yd, t.zeros_like(self._yd))
         self.grad_method = 'finite_difference'
         self._K = self._QT = self._kern_key = None
         self.dependent_attributes = list(self.dependent_attributes)
@@ -725,13 +768,29 @@ class GPGridModel(BaseModel):
             self._QT = K.schur()
         return self._QT
 
+    def _masked_cg(self):
+        """The resident masked solver, cached on (kernel parameters, noise)."""
+        from .linalg import MaskedKronCG
+        K = self._operator()
+        key = (id(K), float(self.noise_var))
+        if self._mcg is None or self._mcg_key != key:
+            self._mcg = MaskedKronCG(K, float(self.noise_var), self._mask, precond=self.precond)
+            self._mcg_key = key
+        return self._mcg
+
     def fit(self):
         self.parameters
         if self._alpha is not None:
             return
         s = float(self.noise_var)
         y = self._yd.reshape(-1, 1)
-        if self.solver == 'exact':
+        if self._mask is not None:
+            x, it, conv, res, tol = self._masked_cg().solve(self._yd, rtol=self.cg_rtol)
+            if not conv:
+                logger.info('masked CG did not converge in %d iterations' % it)
+            self.cg_iters = it
+            self._alpha = x.clone()
+        elif self.solver == 'exact':
             Q, T = self._schur()
             self._alpha = Q.solve_schur(T, y, shift=s).reshape(-1)
         else:
@@ -741,7 +800,75 @@ class GPGridModel(BaseModel):
                 logger.info('CG did not converge in %d iterations' % info)
             self._alpha = x.reshape(-1)
 
+    def _lam_dev(self):
+        """(d, factor orders, concatenated per-factor eigenvalues on the device)."""
+        Q, T = self._schur()
+        lam = [np.asarray(e, dtype=np.float64).reshape(-1) for e in T.diag().K]
+        from . import native
+        return len(lam), native.i64_array([l.size for l in lam]), \
+            dev.to_device(np.concatenate(lam))
+
+    def _kron_row(self, vecs):
+        """kron_f vecs[f] as a device N-vector: the Kronecker product of m_f x 1
+        factors applied to [1] (gg_kron_matvec)."""
+        from .tensors import KronMatrix
+        cols = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1, 1))
+                for v in vecs]
+        one = dev.to_device(np.ones(1))
+        return KronMatrix(cols).matvec_device(one)
+
+    def _masked_log_det_exact(self):
+        """log det(K_oo + s I) = sum_N log(lam_g + s) + log det[((K + s I)^-1)_mm]
+        (the Schur-complement identity on the inverse)."""
+        from . import native
+        s = float(self.noise_var)
+        Q, T = self._schur()
+        full = T.diag().log_det_shifted(s)
+        t = dev.torch()
+        miss = t.nonzero(self._mask == 0).reshape(-1)
+        m = int(miss.numel())
+        if m == 0:
+            return full
+        if m > self.exact_missing_max:
+            raise ValueError("logdet='exact' needs %d exact solves and a %d x %d Cholesky for "
+                             "the missing points, above exact_missing_max=%d; raise it or use "
+                             "logdet='scaled_eigs'" % (m, m, m, self.exact_missing_max))
+        d, ms, lamd = self._lam_dev()
+        sizes = [int(v) for v in ms]
+        Qf = [np.asarray(q, dtype=np.float64) for q in Q.K]
+        B = t.empty((m, m), dtype=t.float64, device=lamd.device)
+        w = dev.empty(self.num_data)
+        for k, g in enumerate(miss.cpu().numpy().tolist()):
+            idx = np.unravel_index(g, sizes)
+            v = self._kron_row([Qf[f][idx[f], :] for f in range(d)])   # Q^T e_g
+            native.check(native.lib().gg_kron_diag_scale(
+                d, ms, native.dptr(lamd), s, native.GG_DIAG_DIVIDE, native.dptr(v),
+                native.dptr(w), native.stream_ptr()), "gg_kron_diag_scale")
+            col = Q.matvec_device(w)
+            B[:, k] = col[miss]
+        B = 0.5 * (B + B.T)
+        return full + dense.Cholesky(B).logdet
+
+    def _masked_log_det_scaled(self):
+        """Wilson's scaled eigenvalues: sum_{i <= n} log((n / N) lam_(i) + s) over
+        the n largest Kronecker eigenvalues (expanded and sorted on the device)."""
+        from . import native
+        s = float(self.noise_var)
+        d, ms, lamd = self._lam_dev()
+        t = dev.torch()
+        N, n = self.num_data, self.num_observed
+        ones = t.ones(N, dtype=t.float64, device=lamd.device)
+        lam = dev.empty(N)
+        native.check(native.lib().gg_kron_diag_scale(
+            d, ms, native.dptr(lamd), 0.0, native.GG_DIAG_MULTIPLY, native.dptr(ones),
+            native.dptr(lam), native.stream_ptr()), "gg_kron_diag_scale")
+        top = t.sort(lam, descending=True).values[:n]
+        return float(t.log(top * (float(n) / float(N)) + s).sum().item())
+
     def _cov_log_det(self):
+        if self._log_det is None and self._mask is not None:
+            self._log_det = (self._masked_log_det_exact() if self.logdet == 'exact'
+                             else self._masked_log_det_scaled())
         if self._log_det is None:
             s = float(self.noise_var)
             if self.logdet == 'exact':
@@ -758,7 +885,7 @@ class GPGridModel(BaseModel):
         self.parameters = parameters
         self.fit()
         ll = -0.5 * (dense.dot(self._yd, self._alpha) + self._cov_log_det()
-                     + self.num_data * np.log(2 * np.pi))
+                     + self.num_observed * np.log(2 * np.pi))
         return np.array([[ll]])
 
     def _out(self, vd):
@@ -770,6 +897,10 @@ class GPGridModel(BaseModel):
         eigenpairs, streamed on the device)."""
         from . import native
         from .tensors import KronMatrix
+        if self._mask is not None and compute_var:
+            raise ValueError("mask=: the grid posterior variance is not available on an "
+                             "incomplete grid; call predict_grid(compute_var=False) for the "
+                             "imputed mean K alpha, or predict(Xnew) for point variances")
         self.fit()
         K = self._operator()
         mean = K.matvec_device(self._alpha)
@@ -808,6 +939,18 @@ class GPGridModel(BaseModel):
         if not compute_var:
             return dense.host(mean).reshape(-1, 1), None
         s = float(self.noise_var)
+        if self._mask is not None:
+            # one masked solve per test row: k* = kron_f k_f(x*) expanded on the
+            # device, v = (K_oo + s I)^-1 k*_o (0 off the observed set)
+            A = [dense.host(Af) if dev.is_device_array(Af) else np.asarray(Af) for Af in Kxz.A]
+            kss = float(self.kern.diag_val)
+            solver = self._masked_cg()
+            var = np.empty(Xnew.shape[0])
+            for j in range(Xnew.shape[0]):
+                ks = self._kron_row([Af[j, :] for Af in A])
+                v = solver.solve(ks, rtol=self.cg_rtol)[0]
+                var[j] = kss - dense.dot(ks, v) + s
+            return dense.host(mean).reshape(-1, 1), var.reshape(-1, 1)
         Q, T = self._schur()
         V2 = []
         for Af, Qf in zip(Kxz.A, Q.K):

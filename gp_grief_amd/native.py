@@ -105,6 +105,14 @@ SIGNATURES = {
     "gg_cg_profile": [_vp, ctypes.c_int],
     "gg_cg_profile_read": [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double),
                            ctypes.c_int],
+    "gg_cgm_work_elems": [_vp, _c_i64p],
+    "gg_cgm_create": [_vp, ctypes.c_double, _vp, _c_dp, ctypes.POINTER(ctypes.c_void_p)],
+    "gg_cgm_destroy": [_vp],
+    "gg_cgm_set_precond": [_vp, _vp, _c_dp],
+    "gg_cgm_start": [_vp, _c_dp, _c_dp, ctypes.c_double, ctypes.c_double, _vp],
+    "gg_cgm_iterate": [_vp, ctypes.c_int, ctypes.c_int, _vp],
+    "gg_cgm_status": [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp],
     "gg_lanczos_probe": [_vp, ctypes.c_double, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                          _c_dp, ctypes.POINTER(ctypes.c_double),
                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), _vp],

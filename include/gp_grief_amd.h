@@ -322,6 +322,42 @@ int gg_cg_close_finish(gg_cg* cg, const double* rr_dev, gg_stream stream);
 int gg_cg_profile(gg_cg* cg, int enable);
 int gg_cg_profile_read(gg_cg* cg, int* n_matvecs, double* mode_ms, int mode_ms_len);
 
+/* ------------------------------------------- masked CG (incomplete grids)
+ * CG on A x = W b, A = W K W + shift I, W = diag(mask), x0 = 0: the grid GP
+ * with missing observations (Saatci 2011; Wilson et al. 2014).  x, r and p are
+ * zero off the observed set at every iteration, so x restricted to it solves
+ * (K_oo + shift I) x_o = b_o.  b at the missing points is never used (it may
+ * be NaN).  The recurrence, stopping rule and iteration count are those of
+ * gg_cg_* (textbook recurrence, grid basis); with a mask of all ones the
+ * iterates are the same.  No reference counterpart (the reference has no CG,
+ * SURVEY 0.2).
+ * mask_dev: n bytes on the device, any alignment, nonzero = observed; the
+ * handle keeps the pointer (the caller keeps the buffer alive).  work_dev:
+ * gg_cgm_work_elems doubles.  GG_ERR_VALUE for a non-square operator, a NULL
+ * mask or shift <= 0 (W K W alone is singular).                             */
+typedef struct gg_cgm gg_cgm;
+int gg_cgm_work_elems(const gg_kron* K, int64_t* elems);
+int gg_cgm_create(const gg_kron* K, double shift, const uint8_t* mask_dev, double* work_dev,
+                  gg_cgm** out);
+int gg_cgm_destroy(gg_cgm* cgm);
+/* Optional preconditioner (before gg_cgm_start; Q == NULL: off):
+ * z = W Q diag(1 / (lam + shift)) Q^T r, the exact inverse on the full grid.
+ * Q: the operator of the per-factor eigenvectors of K (same factor orders),
+ * lam_dev: the concatenated per-factor eigenvalues (as gg_kron_diag_scale).
+ * Two more Kronecker matvecs, a decoded divide and a dot per iteration; the
+ * handle allocates its two extra vectors.  The stopping test stays on |r|.   */
+int gg_cgm_set_precond(gg_cgm* cgm, const gg_kron* Q, const double* lam_dev);
+/* r = select(mask, b, 0), x = 0, tolerance max(atol, rtol |W b|).  b_dev and
+ * x_dev at any 8-byte aligned address (16-byte: the double2 kernels).       */
+int gg_cgm_start(gg_cgm* cgm, const double* b_dev, double* x_dev, double rtol, double atol,
+                 gg_stream stream);
+/* Up to max_iters iterations; the host polls the device's done flag every
+ * check_every iterations (<= 0: never) and stops issuing work once it is set;
+ * successive calls continue the same recurrence.                            */
+int gg_cgm_iterate(gg_cgm* cgm, int max_iters, int check_every, gg_stream stream);
+int gg_cgm_status(gg_cgm* cgm, int* iters, int* converged, double* resid_norm, double* tol,
+                  gg_stream stream); /* synchronising */
+
 /* ----------------------------------------------- Lanczos (SLQ log-det, P1)
  * k steps of three-term Lanczos on (K + shift I) from z / ||z|| where z is the
  * Rademacher probe (seed, probe) (oracle/cg.py probe_signs).  Writes the
