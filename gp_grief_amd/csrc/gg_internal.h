@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/gp_grief_amd.h"
 
@@ -248,7 +249,33 @@ __device__ __forceinline__ double block_sum(double v) {
   }
   return s;
 }
+
+// ---- the unnormalised Lanczos recurrence's one-thread scalar kernels
+// (gg_vec.hip), shared with the masked probe (gg_lzm.hip).
+// lzs: [0] sV, [1] sP, [2] cy, [3] cu, [4] cp
+__global__ void lz_coef_kernel(double* __restrict__ lzs, const double* __restrict__ dot,
+                               double* __restrict__ alpha_out,
+                               const double* __restrict__ beta_prev);
+__global__ void lz_beta_kernel(double* __restrict__ lzs, double* __restrict__ beta);
 #endif
+
+// RAII set of HIP events (timed Lanczos, calibration)
+struct EventSet {
+  std::vector<hipEvent_t> ev;
+  explicit EventSet(size_t n) {
+    ev.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+      hipEvent_t e;
+      GG_HIP(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+  }
+  ~EventSet() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  EventSet(const EventSet&) = delete;
+  EventSet& operator=(const EventSet&) = delete;
+};
 
 // ---- the sharded CG's scalar state (gg_vec.hip gg_cgs), for the fused
 // sharded phase 1 in gg_kron.hip ----

@@ -845,24 +845,6 @@ static KronDiag make_diag(int d, const int64_t* m, int64_t* n_out) {
 
 // ------------------------------------------------------------------- CG state
 namespace gg {
-// RAII set of HIP events (timed Lanczos, calibration)
-struct EventSet {
-  std::vector<hipEvent_t> ev;
-  explicit EventSet(size_t n) {
-    ev.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-      hipEvent_t e;
-      GG_HIP(hipEventCreate(&e));
-      ev.push_back(e);
-    }
-  }
-  ~EventSet() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-  EventSet(const EventSet&) = delete;
-  EventSet& operator=(const EventSet&) = delete;
-};
-
 // a handle's scalar block: zeroed, with the cancellation threshold of the
 // knob snapshot (GG_CG_CANCEL_TOL, tests: forces the repair / restart paths)
 static void scalars_clear(CgScalars* sc) {

@@ -14,7 +14,10 @@ Device solvers (no reference implementation exists):
                    optionally preconditioned by the Kronecker eigenpairs.
   slq_logdet    -- stochastic Lanczos quadrature, Lanczos on the device
                    (gg_lanczos_probe); the k x k tridiagonal eigensolve of the
-                   quadrature is host-side (k <= a few hundred).
+                   quadrature is host-side (k <= a few hundred).  With mask=:
+                   Lanczos on (W K W + shift I) from probes zeroed at the
+                   missing points (gg_lanczos_probe_masked), the estimator of
+                   log det(K_oo + shift I) on an incomplete grid.
 """
 import ctypes
 import logging
@@ -489,7 +492,7 @@ def lanczos_info(K):
     return bool(b.value), L.value
 
 
-def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False):
+def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False, mask=None):
     """Device Lanczos on (K + shift I) from a Rademacher probe: (alphas, betas).
 
     work: optional device workspace of >= 4 N elements (allocated here
@@ -497,11 +500,24 @@ def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False):
     per step run) and the summed time of each mode-product position
     (gg_lanczos_probe_timed): (alphas, betas, step_ms, launch_ms); the
     once-per-probe closing pass (the last beta's streaming pass, after the
-    last step) is left in lanczos_tridiag.closing_ms."""
+    last step) is left in lanczos_tridiag.closing_ms.
+
+    mask (bool / uint8, N entries, numpy or device; nonzero = observed; a
+    device uint8 tensor is used where it lies, at any alignment): Lanczos on
+    (W K W + shift I), W = diag(mask), from the same probe zeroed at the
+    missing points and normalised by the observed count
+    (gg_lanczos_probe_masked) -- the tridiagonal of (K_oo + shift I).  The
+    count the library made is left in lanczos_tridiag.n_observed; timed=True
+    returns (alphas, betas, step_ms)."""
     from . import device as dev
     from . import native
     dk = K._device()
     n = int(K.shape[0])
+    if mask is not None:
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("Lanczos needs steps >= 1")
+        md = _mask_device_bytes(mask, n)
     if work is None:
         work = dev.empty(4 * n)
     elif int(work.numel()) < 4 * n:
@@ -509,6 +525,23 @@ def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False):
     a = (ctypes.c_double * steps)()
     b = (ctypes.c_double * steps)()
     done = ctypes.c_int()
+    if mask is not None:
+        nobs = ctypes.c_int64()
+        args = (dk.h, float(shift), ctypes.c_void_p(md.data_ptr()), int(seed), int(probe), steps,
+                native.dptr(work), a, b, ctypes.byref(done), ctypes.byref(nobs))
+        if timed:
+            sm = (ctypes.c_double * steps)()
+            native.check(native.lib().gg_lanczos_probe_masked_timed(
+                *(args + (sm, native.stream_ptr()))), "gg_lanczos_probe_masked_timed")
+        else:
+            native.check(native.lib().gg_lanczos_probe_masked(*(args + (native.stream_ptr(),))),
+                         "gg_lanczos_probe_masked")
+        lanczos_tridiag.n_observed = int(nobs.value)
+        k = done.value
+        out = np.array(a[:k]), np.array(b[:max(k - 1, 0)])
+        if timed:
+            return out + ([sm[j] for j in range(steps)],)
+        return out
     if timed:
         d = len(dk._keep)
         sm = (ctypes.c_double * steps)()
@@ -530,15 +563,42 @@ def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False):
 
 
 lanczos_tridiag.closing_ms = None
+lanczos_tridiag.n_observed = None
 
 
-def slq_logdet(K, shift, probes=8, steps=30, seed=0):
-    """Stochastic Lanczos quadrature estimate of log det(K + shift I)."""
+def _mask_device_bytes(mask, n):
+    """The mask as n device bytes for the masked probe: a contiguous device
+    uint8 / bool tensor is taken where it lies (any alignment, no copy and no
+    count: the library counts), anything else goes through _mask_to_device."""
+    from . import device as dev
+    t = dev.torch()
+    if isinstance(mask, t.Tensor) and mask.is_cuda and mask.dtype in (t.uint8, t.bool) \
+            and mask.is_contiguous():
+        if mask.numel() != n:
+            raise ValueError("mask must have %d entries, not %d" % (n, mask.numel()))
+        return mask.detach().reshape(-1)
+    return _mask_to_device(mask, n)[0]
+
+
+def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None):
+    """Stochastic Lanczos quadrature estimate of log det(K + shift I):
+    (mean, per-probe estimates).
+
+    mask (as lanczos_tridiag): the estimate of log det(K_oo + shift I) on the
+    observed points -- each probe's quadrature is scaled by the observed count
+    and steps is capped at it; its cost is probes x steps Kronecker matvecs
+    whatever the number of missing points."""
     n = int(K.shape[0])
+    scale, kw = n, {}
+    if mask is not None:
+        from . import device as dev
+        md, scale = _mask_to_device(mask, n)
+        steps = min(int(steps), scale)
+        kw = dict(work=dev.empty(4 * n), mask=md)
     ests = []
     for j in range(probes):
-        a, b = lanczos_tridiag(K, shift, steps, seed=seed, probe=j)
+        a, b = lanczos_tridiag(K, shift, steps, seed=seed, probe=j, **kw)
         T = np.diag(a) + np.diag(b, 1) + np.diag(b, -1)
         theta, U = np.linalg.eigh(T)
-        ests.append(float(n) * float(np.sum(U[0, :] ** 2 * np.log(theta))))
+        ests.append(float(scale) * float(np.sum(U[0, :] ** 2 * np.log(theta))))
     return float(np.mean(ests)), np.array(ests)

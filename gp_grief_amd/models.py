@@ -17,8 +17,9 @@
                  exact eigen-solve, exact or Lanczos (SLQ) log det, posterior
                  mean and latent variance on the grid.  With mask= the grid is
                  incomplete: masked device CG (linalg.MaskedKronCG), exact
-                 (Schur identity) or scaled-eigenvalue log det, imputed grid
-                 mean, off-grid mean and variance.
+                 (Schur identity), scaled-eigenvalue or masked-SLQ
+                 (logdet='lanczos') log det, imputed grid mean, off-grid mean
+                 and variance.
 
 Device state keeps the reference's attribute names (_Phi, _A, _P, _Pchol,
 _alpha, _alpha_p) holding CUDA tensors (or small host arrays where the
@@ -682,7 +683,7 @@ class GPGridModel(BaseModel):
     solver: 'exact' (per-factor eigendecomposition, two device Kron matvecs
     and a decoded divide; the default on a complete grid) or 'cg' (device CG,
     linalg.KronCG; the default, and the only choice, with mask=).  logdet: 'exact'
-    (streamed over the grid on the device) or 'slq'.  Y (N,1) numpy or CUDA
+    (streamed over the grid on the device) or 'slq' (with mask=: below).  Y (N,1) numpy or CUDA
     tensor; results come back in the same kind.  grad_method is finite
     differences over (noise, kernel parameters) like the reference's
     kernel-parameter path.
@@ -698,7 +699,11 @@ class GPGridModel(BaseModel):
     vectors and a device Cholesky, for m <= exact_missing_max (a cost guard on
     m Kronecker matvecs and an m x m Cholesky, not a tuned value); or
     'scaled_eigs' -- Wilson's approximation sum_{i <= n} log((n / N) lam_(i) + s)
-    over the n largest Kronecker eigenvalues.
+    over the n largest Kronecker eigenvalues; or 'lanczos' -- stochastic Lanczos
+    quadrature on (W K W + s I) from masked probes (slq_probes, slq_steps, seed;
+    linalg.slq_logdet(mask=)): the one choice that is an estimator of the log
+    det at any number of missing points, its per-probe estimates kept in
+    slq_estimates.
     """
 
     def __init__(self, xg, Y, kern, noise_var=1., solver=None, logdet='exact',
@@ -712,6 +717,9 @@ class GPGridModel(BaseModel):
         if solver not in ('exact', 'cg'):
             raise ValueError("solver must be 'exact' or 'cg'")
         if mask is None:
+            if logdet == 'lanczos':
+                raise ValueError("logdet='lanczos' is the masked estimator and needs mask=; "
+                                 "a complete grid uses logdet='slq'")
             if logdet not in ('exact', 'slq'):
                 raise ValueError("logdet must be 'exact' or 'slq'")
             if precond is not None:
@@ -721,9 +729,9 @@ class GPGridModel(BaseModel):
                 raise ValueError("mask=: solver='exact' does not apply to an incomplete grid "
                                  "(the eigendecomposition no longer diagonalises it); "
                                  "use solver='cg'")
-            if logdet not in ('exact', 'scaled_eigs'):
-                raise ValueError("mask=: logdet must be 'exact' (Schur identity) or "
-                                 "'scaled_eigs', not %r" % (logdet,))
+            if logdet not in ('exact', 'scaled_eigs', 'lanczos'):
+                raise ValueError("mask=: logdet must be 'exact' (Schur identity), "
+                                 "'scaled_eigs' or 'lanczos', not %r" % (logdet,))
             if precond not in (None, 'kron'):
                 raise ValueError("precond must be None or 'kron'")
         self.xg = xg
@@ -738,6 +746,7 @@ class GPGridModel(BaseModel):
         self.dim_noise_var = float(dim_noise_var)
         self.cg_rtol = float(cg_rtol)
         self.slq = (int(slq_probes), int(slq_steps), int(seed))
+        self.slq_estimates = None
         self.precond = precond
         self.exact_missing_max = int(exact_missing_max)
         self._mask = self._mcg = self._mcg_key = None
@@ -865,10 +874,27 @@ class GPGridModel(BaseModel):
         top = t.sort(lam, descending=True).values[:n]
         return float(t.log(top * (float(n) / float(N)) + s).sum().item())
 
+    def _masked_log_det_lanczos(self):
+        """Stochastic Lanczos quadrature on (W K W + s I) from masked probes
+        (linalg.slq_logdet(mask=)): an estimator of log det(K_oo + s I) whose
+        error shrinks with probes and steps, at probes x steps Kronecker matvecs
+        whatever the number of missing points.  The per-probe estimates stay in
+        slq_estimates (their std / sqrt(probes) is the standard error); the seed
+        is fixed, so the objective is deterministic."""
+        from .linalg import slq_logdet
+        probes, steps, seed = self.slq
+        mean, self.slq_estimates = slq_logdet(self._operator(), float(self.noise_var),
+                                              probes=probes, steps=steps, seed=seed,
+                                              mask=self._mask)
+        return mean
+
     def _cov_log_det(self):
         if self._log_det is None and self._mask is not None:
-            self._log_det = (self._masked_log_det_exact() if self.logdet == 'exact'
-                             else self._masked_log_det_scaled())
+            if self.logdet == 'lanczos':
+                self._log_det = self._masked_log_det_lanczos()
+            else:
+                self._log_det = (self._masked_log_det_exact() if self.logdet == 'exact'
+                                 else self._masked_log_det_scaled())
         if self._log_det is None:
             s = float(self.noise_var)
             if self.logdet == 'exact':

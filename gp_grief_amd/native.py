@@ -122,6 +122,15 @@ SIGNATURES = {
                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                _vp],
     "gg_lanczos_info": [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
+    "gg_lanczos_probe_masked": [_vp, ctypes.c_double, _vp, ctypes.c_uint64, ctypes.c_int,
+                                ctypes.c_int, _c_dp, ctypes.POINTER(ctypes.c_double),
+                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                _c_i64p, _vp],
+    "gg_lanczos_probe_masked_timed": [_vp, ctypes.c_double, _vp, ctypes.c_uint64, ctypes.c_int,
+                                      ctypes.c_int, _c_dp, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_int), _c_i64p,
+                                      ctypes.POINTER(ctypes.c_double), _vp],
     "gg_probe_fill": [ctypes.c_uint64, ctypes.c_int, _c_dp, ctypes.c_int64, _vp],
     "gg_sym_eig_batched": [ctypes.c_int, _c_i64p, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
                            ctypes.c_int, _vp],

@@ -387,6 +387,40 @@ int gg_lanczos_probe_timed(const gg_kron* K, double shift, uint64_t seed, int pr
  * *launches: the launches per step (the positions of launch_ms_host, the rest
  * of its d entries 0).                                                       */
 int gg_lanczos_info(const gg_kron* K, int* block, int* launches);
+/* --------------------------------- masked Lanczos (incomplete grids, SLQ)
+ * k steps of three-term Lanczos on A = W K W + shift I, W = diag(mask), from
+ * v0 = select(mask, z, 0) / sqrt(n_obs), z the Rademacher probe (seed, probe)
+ * over all n grid points (gg_probe_fill, oracle/cg.py probe_signs, indexed by
+ * grid position): the unmasked probe with the missing entries zeroed.  Every
+ * Lanczos vector is zero off the observed set, so the tridiagonal is that of
+ * K_oo + shift I from the compressed probe: the quadrature behind
+ * log det(K_oo + shift I), the half of the marginal likelihood the masked CG
+ * (gg_cgm_*) does not give.  Grid basis (W is not diagonal in the
+ * parity-block basis); per step the matvec plus one streaming pass, w =
+ * select(mask, cy Y, 0) + cu u + cp u_prev with |w|^2 (3 reads, 1 write and
+ * the mask, n / 8 of one).  With a mask of all ones the tridiagonal is the
+ * grid-basis gg_lanczos_probe's to rounding.  No reference counterpart (SLQ
+ * is absent from the reference).
+ * mask_dev: n bytes on the device, any alignment, nonzero = observed; nothing
+ * is kept after the call.  The library counts the observed points itself (one
+ * reduction over the mask), normalises by the count on the device and returns
+ * it in *n_observed (may be NULL).  work_dev: 4 * n elements.  alphas[k],
+ * betas[k] go to host memory (the one synchronisation); breakdown and
+ * *steps_done as gg_lanczos_probe.  GG_ERR_VALUE for a NULL mask, a
+ * non-square operator or factors, steps < 1, shift < 0 (all before any
+ * launch) or a mask with no observed point.                                  */
+int gg_lanczos_probe_masked(const gg_kron* K, double shift, const uint8_t* mask_dev,
+                            uint64_t seed, int probe, int steps, double* work_dev,
+                            double* alphas_host, double* betas_host, int* steps_done,
+                            int64_t* n_observed, gg_stream stream);
+/* The same with live per-step timing: step_ms_host[j] (steps entries) is the
+ * HIP-event time of step j on the stream -- its matvec, update pass and scalar
+ * kernels; the first event follows the start vector and the count.           */
+int gg_lanczos_probe_masked_timed(const gg_kron* K, double shift, const uint8_t* mask_dev,
+                                  uint64_t seed, int probe, int steps, double* work_dev,
+                                  double* alphas_host, double* betas_host, int* steps_done,
+                                  int64_t* n_observed, double* step_ms_host,
+                                  gg_stream stream);
 int gg_probe_fill(uint64_t seed, int probe, double* z_dev, int64_t n, gg_stream stream);
 
 /* --------------------------------------- per-factor symmetric eigensolver
