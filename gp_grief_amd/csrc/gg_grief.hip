@@ -420,11 +420,10 @@ static void launch_phi_pair(dim3 grid, size_t lds, hipStream_t s, const double* 
 // the pair kernel for d <= 8; false: not taken (the caller launches the other)
 static bool launch_phi_pair_d(hipStream_t s, const double* L, const double* S, int U, int64_t n,
                               const int* cidx, int d, const double* ll, int p, double* phi) {
-  static const bool on = [] {
-    const char* e = gg::knob("GG_PHI_PAIR");   // A/B knob: 0 = the 256-column kernel
-    return !(e != nullptr && atoi(e) == 0);
-  }();
-  if (!on || d > 8 || (p & 1) || (reinterpret_cast<uintptr_t>(phi) & 15)) return false;
+  // A/B knob: 0 = the 256-column kernel; read from the snapshot at every call
+  // so that gg_knobs_reload governs it (like GG_GRIEF_TABLES)
+  const char* e = gg::knob("GG_PHI_PAIR");
+  if ((e != nullptr && atoi(e) == 0) || d > 8 || (p & 1) || (reinterpret_cast<uintptr_t>(phi) & 15)) return false;
   constexpr int kR = kPhiRows;
   const size_t lds = (size_t)kR * U * sizeof(double);
   if (lds > 160 * 1024) return false;
@@ -486,21 +485,23 @@ __global__ __launch_bounds__(256) void expand_skc_kernel(const double* __restric
                                                          double* __restrict__ out,
                                                          int* __restrict__ sign) {
   const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y;
-  if (a >= n || j >= p) return;
-  double acc = logged ? 0.0 : 1.0;
-  int sg = 1;
-  for (int f = 0; f < d; ++f) {
-    const double v = X[(int64_t)cidx[(int64_t)j * d + f] * n + a];
-    if (logged) {
-      sg *= v > 0.0 ? 1 : (v < 0.0 ? -1 : 0);
-      acc += log(fabs(v == 0.0 ? 1.0 : v));
-    } else {
-      acc *= v;
+  if (a >= n) return;
+  // blockIdx.y strides over j: gridDim.y is capped at 65535, p is not
+  for (int64_t j = blockIdx.y; j < p; j += gridDim.y) {
+    double acc = logged ? 0.0 : 1.0;
+    int sg = 1;
+    for (int f = 0; f < d; ++f) {
+      const double v = X[(int64_t)cidx[j * d + f] * n + a];
+      if (logged) {
+        sg *= v > 0.0 ? 1 : (v < 0.0 ? -1 : 0);
+        acc += log(fabs(v == 0.0 ? 1.0 : v));
+      } else {
+        acc *= v;
+      }
     }
+    out[j * n + a] = acc;
+    if (logged) sign[j * n + a] = sg;
   }
-  out[(int64_t)j * n + a] = acc;
-  if (logged) sign[(int64_t)j * n + a] = sg;
 }
 
 }  // namespace gg
@@ -618,10 +619,9 @@ int gg_expand_skc(const double* x_dev, int U, int64_t n, const int* cidx_dev, in
                   int logged, double* out_dev, int* sign_dev, gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(x_dev && cidx_dev && out_dev && (!logged || sign_dev), GG_ERR_VALUE, "NULL");
-    GG_REQUIRE(U >= 1 && d >= 1 && p >= 0 && n >= 0 && p < 65536, GG_ERR_VALUE,
-               "bad expand_SKC geometry");
+    GG_REQUIRE(U >= 1 && d >= 1 && p >= 0 && n >= 0, GG_ERR_VALUE, "bad expand_SKC geometry");
     if (n == 0 || p == 0) return;
-    dim3 grid((unsigned)gg::ceil_div(n, 256), (unsigned)p);
+    dim3 grid((unsigned)gg::ceil_div(n, 256), (unsigned)std::min(p, 65535));
     hipLaunchKernelGGL(gg::expand_skc_kernel, grid, dim3(256), 0, gg::as_stream(stream), x_dev,
                        n, cidx_dev, d, p, logged, out_dev, sign_dev);
     GG_LAUNCH_CHECK();

@@ -485,7 +485,15 @@ int gg_cov(int kind, double variance, double lengthscale, int dims, const double
  * X[u][a] = sum_k qsel[u][k] k(xg[k], x[a * x_stride]); writes
  * ltab[a*U + col0 + u] = log|X| (0 where X == 0) and stab = sign(X), or with
  * stab_dev == NULL the value table ltab[a*U + col0 + u] = X (half the bytes;
- * what gg_grief_phi needs).                                                  */
+ * what gg_grief_phi needs).  Only columns [col0, col0 + u) of rows a < n of
+ * the n x U tables are written (U may exceed the columns any factor writes;
+ * the rest keeps the caller's values), and of x only the n elements
+ * x[a * x_stride] are read (for gg_grief_tables_all x[a * x_stride +
+ * x_offsets[f]]): x may be a column of a wider array.  m >= 1, u >= 1,
+ * 0 <= col0, col0 + u <= U (gg_grief_tables_all: 0 <= x_offsets[f] <
+ * x_stride, nf >= 1), else GG_ERR_VALUE before any launch; n == 0 is GG_OK
+ * and writes nothing.  GG_GRIEF_TABLES=0 (gg_knobs_reload) selects the
+ * lane-quad kernel instead of the MFMA one.                                  */
 int gg_grief_tables(int kind, double variance, double lengthscale, const double* x_dev,
                     int64_t x_stride, int64_t n, const double* xg_dev, int m,
                     const double* qsel_dev, int u, double* ltab_dev, double* stab_dev, int U,
@@ -504,7 +512,16 @@ int gg_grief_tables_all(int nf, const int* kinds, const double* variances,
  * (GriefKernel.cov, gp_grief/kern/grief_kernel.py:96-104); cidx: p x d int32.
  * stab_dev == NULL: ltab is the value table (X itself) and Phi[a][j] =
  * prod_f ltab[a][c_jf] * exp(-log_lam[j] / 2).  transposed != 0 writes Phi^T
- * (p x n).                                                                   */
+ * (p x n).  Limits (GG_ERR_VALUE before any launch, Phi untouched):
+ * 1 <= d <= 64, p >= 1, and U >= 1 capped by the 160 KiB of LDS a block
+ * stages its table rows in: row-major 64 * 8 U + 1024 d <= 163840 bytes
+ * (U <= 320 - 2 d), transposed 32 * 8 U + 67584 + 1024 d <= 163840
+ * (U <= 376 - 4 d); beyond it the error is "too many selected eigenvector
+ * rows".  n == 0 is GG_OK and writes nothing.  Only the table columns some
+ * cidx entry names are read into Phi.  Row-major output with even p, d <= 8
+ * and a 16-byte aligned phi_dev takes the column-pair kernel (GG_PHI_PAIR=0
+ * at gg_knobs_reload: the 256-column kernel, as for any other shape); the
+ * factors are multiplied in the same order in every kernel.                  */
 int gg_grief_phi(const double* ltab_dev, const double* stab_dev, int U, int64_t n,
                  const int* cidx_dev, int d, const double* log_lam_dev, int p, int transposed,
                  double* phi_dev, gg_stream stream);
@@ -512,7 +529,8 @@ int gg_grief_phi(const double* ltab_dev, const double* stab_dev, int U, int64_t 
  * stacked unique rows X (U x n row-major: rows row0_f .. row0_f + u_f - 1 are
  * (K_f)[unique_f] . C_f) and cidx (p x d int32, c_jf = row0_f + inverse_f[j]):
  * logged -> out = sum_f log|X[c_jf]| (0 for X == 0), sign_dev = prod_f sign;
- * else out = prod_f X[c_jf].  out: p x n.                                     */
+ * else out = prod_f X[c_jf].  out: p x n.  Any p >= 0 and n >= 0 (either 0:
+ * GG_OK, nothing written); logged with sign_dev == NULL is GG_ERR_VALUE.      */
 int gg_expand_skc(const double* x_dev, int U, int64_t n, const int* cidx_dev, int d, int p,
                   int logged, double* out_dev, int* sign_dev, gg_stream stream);
 

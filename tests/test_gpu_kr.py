@@ -144,3 +144,106 @@ def test_grid_predict_offgrid_larger(gg):
     mo, vo = oracle.grid_offgrid_predict(factors, blocks, np.ones(64), alpha, s)
     assert rel(mean, mo) < 1e-9
     assert rel(var - s, vo) < 1e-8
+
+
+# ---- gg_kr_contract through ctypes at the NT switch points, deep d and its
+# scratch boundary.  Bound (elementwise, u = 2^-53): K = m_{d-1} products
+# accumulated per outer row, the rows of a column summed in any order (outer =
+# prod m_f, f < d - 1, of them), d - 1 weight multiplies:
+#   |got - ref| <= (K + outer + d) u sum_g |c_g| prod_f |U_f[j][g_f]|
+# against the contraction accumulated in long double.
+def _kr_consts():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "gp_grief_amd", "csrc", "gg_kr.hip")).read()
+    return {k: int(re.search(r"\b%s\s*=\s*(\d+)" % k, src).group(1))
+            for k in ("kSMaxWG", "kKrMaxSplits", "kKrThreads", "kKrMaxD")}
+
+
+def _kr_need(ms, M):
+    """The scratch the path gg_kr_contract takes requires (its GG_REQUIREs)."""
+    k = _kr_consts()
+    outer = int(np.prod(ms[:-1])) if len(ms) > 1 else 1
+    if len(ms) - 1 <= 7:                      # fused streaming kernel: gy partial rows
+        nt = 1 if M <= 16 else (4 if M <= 64 else 8)
+        groups = -(-(-(-outer // 16)) // 4)
+        gx = -(-M // (16 * nt))
+        return max(1, min(groups, max(1, k["kSMaxWG"] // gx))) * M
+    bx = -(-M // k["kKrThreads"])             # two-pass: S partial rows + one row of T
+    return (max(1, min(k["kKrMaxSplits"], -(-4096 // bx))) + 1) * M
+
+
+def _kr_call(ms, M, work_elems=None, d=None, seed=0):
+    """(status, out with its guards checked, blocks, c) of one gg_kr_contract
+    call with exactly work_elems (default: what the path requires) of scratch."""
+    import ctypes
+    import torch
+    from gp_grief_amd import native
+    rng = np.random.default_rng(1000 * len(ms) + M + seed)
+    blocks = [rng.standard_normal((M, m)) for m in ms]
+    c = rng.standard_normal(int(np.prod(ms)))
+    need = _kr_need(ms, max(M, 1)) if work_elems is None else work_elems
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+    uts = [dev(b.T) for b in blocks[:-1]]
+    ulast, cd = dev(blocks[-1]), dev(c)
+    guard = np.full(64, np.nan)
+    out = dev(np.concatenate([guard, np.full(M, np.nan), guard]))
+    work = dev(np.full(max(need, 1) + 64, np.nan))
+    ptrs = (ctypes.c_void_p * max(1, len(uts)))(*[native.dptr(u) for u in uts])
+    st = native.lib().gg_kr_contract(
+        len(ms) if d is None else d, native.i64_array(ms), native.dptr(cd), native.dptr(ulast),
+        ptrs, M, ctypes.c_void_p(out.data_ptr() + 8 * 64), native.dptr(work), need,
+        native.stream_ptr())
+    o = out.cpu().numpy()
+    assert np.all(np.isnan(o[:64])) and np.all(np.isnan(o[64 + M:])), "out guard written"
+    assert np.all(np.isnan(work.cpu().numpy()[max(need, 1):])), "written past work_elems"
+    return st, o[64:64 + M], blocks, c
+
+
+def _kr_check(ms, M):
+    from grief_abi_ref import kr_ref
+    st, got, blocks, c = _kr_call(ms, M)
+    assert st == 0
+    ref, mag = kr_ref(blocks, c)
+    outer = int(np.prod(ms[:-1])) if len(ms) > 1 else 1
+    bound = (ms[-1] + outer + len(ms)) * 2.0 ** -53 * mag
+    err = np.abs(got.astype(np.longdouble) - ref)
+    print("gg_kr_contract ms %s M %d: worst err / bound %.4f" % (ms, M, float((err / bound).max())))
+    assert not np.any(np.isnan(got)) and np.all(err <= bound), (ms, M, float((err / bound).max()))
+    assert rel(ref, oracle.kr_contract(blocks, c)) < 1e-13
+    return st
+
+
+@pytest.mark.parametrize("M", [16, 17, 64, 65, 128])
+def test_kr_contract_nt_switch_points(gg, M):
+    """M = 16 | 17 and 64 | 65: the streaming kernel's NT = 1 | 4 | 8 tiles per
+    pass; 128: one full pass of NT = 8."""
+    _kr_check([5, 6, 7], M)
+
+
+@pytest.mark.parametrize("K", [1, 15, 16, 17])
+def test_kr_contract_single_factor(gg, K):
+    """d = 1 (no weights, NF = 0) around the 16-deep staged k chunk."""
+    _kr_check([K], 19)
+
+
+@pytest.mark.parametrize("ms", [[2] * 11 + [3], [1] * 28 + [2, 2, 2, 3]],
+                         ids=["d12", "d32"])
+def test_kr_contract_deep(gg, ms):
+    """The two-pass path (GEMM + odometer column sum) beyond d = 9."""
+    _kr_check(ms, 19)
+
+
+def test_kr_contract_limits(gg):
+    """d = 33 and a scratch one element short of what the taken path needs are
+    refused before any launch (out untouched); M = 0 is a no-op."""
+    k = _kr_consts()
+    st, out, _, _ = _kr_call([1] * k["kKrMaxD"] + [2], 3, d=k["kKrMaxD"] + 1)
+    assert st == -1 and np.all(np.isnan(out))
+    assert _kr_call([5, 6, 7], 0)[0] == 0
+    for ms, M in [([5, 6, 7], 17), ([40, 41, 7], 65), ([2] * 11 + [3], 19)]:
+        need = _kr_need(ms, M)
+        st, out, _, _ = _kr_call(ms, M, work_elems=need - 1)
+        assert st == -1 and np.all(np.isnan(out)), (ms, M)
+        assert _kr_check(ms, M) == 0          # exactly `need` runs and meets the bound
