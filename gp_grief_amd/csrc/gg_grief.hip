@@ -73,6 +73,55 @@ __global__ __launch_bounds__(256) void cov_kernel(int kind, double var, double l
   }
 }
 
+// d k / d lengthscale of stationary(), r = sqrt(d2) / ls:
+//   RBF k r^2 / ls (0 under the delta rule), Exponential k r / ls,
+//   Matern32 var 3 r^2 / ls e^{-sqrt3 r}, Matern52 var (5 r^2 / 3 ls)(1 + sqrt5 r) e^{-sqrt5 r}
+__device__ __forceinline__ double stationary_dls(int kind, double d2, double var, double ls) {
+  switch (kind) {
+    case kRBF: {
+      if (ls < 1e-6) return 0.0;
+      const double r2 = d2 / (ls * ls);
+      return var * exp(-0.5 * r2) * (r2 / ls);
+    }
+    case kExponential: {
+      const double r = sqrt(d2) / ls;
+      return var * exp(-r) * (r / ls);
+    }
+    case kMatern32: {
+      const double r = sqrt(d2) / ls;
+      const double s3 = 1.7320508075688772;
+      return var * (3.0 * r * r / ls) * exp(-s3 * r);
+    }
+    default: {
+      const double r2 = d2 / (ls * ls);
+      const double r = sqrt(r2);
+      const double s5 = 2.23606797749979;
+      return var * ((5.0 / 3) * r2 / ls) * (1.0 + s5 * r) * exp(-s5 * r);
+    }
+  }
+}
+
+// out[i][j] = d k(x_i, z_j) / d variance (which 0: k at unit variance) or
+// / d lengthscale (which 1); x: N x D, z: M x D row-major
+__global__ __launch_bounds__(256) void cov_grad_param_kernel(int kind, double var, double ls,
+                                                             int D, const double* __restrict__ x,
+                                                             int64_t N,
+                                                             const double* __restrict__ z,
+                                                             int64_t M, int which,
+                                                             double* __restrict__ out) {
+  const int64_t total = N * M;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = e / M, j = e - i * M;
+    double d2 = 0.0;
+    for (int k = 0; k < D; ++k) {
+      const double t = x[i * D + k] - z[j * D + k];
+      d2 = fma(t, t, d2);
+    }
+    out[e] = which == 0 ? stationary(kind, d2, 1.0, ls) : stationary_dls(kind, d2, var, ls);
+  }
+}
+
 constexpr int kUG = 16;  // selected eigenvector rows per thread
 constexpr int kTQ = 4;   // lanes per data point: each takes every kTQ-th grid point
 
@@ -521,6 +570,23 @@ int gg_cov(int kind, double variance, double lengthscale, int dims, const double
     const int nb = (int)std::min<int64_t>(8192, gg::ceil_div(total, 256));
     hipLaunchKernelGGL(gg::cov_kernel, dim3(nb), dim3(256), 0, gg::as_stream(stream), kind,
                        variance, lengthscale, dims, x_dev, nx, z_dev, nz, mode, out_dev);
+    GG_LAUNCH_CHECK();
+  });
+}
+
+int gg_cov_grad_param(int kind, double variance, double lengthscale, int dims,
+                      const double* x_dev, int64_t nx, const double* z_dev, int64_t nz,
+                      int which, double* out_dev, gg_stream stream) {
+  return gg::guard([&] {
+    GG_REQUIRE(kind >= 0 && kind <= 3, GG_ERR_VALUE, "unknown kernel kind");
+    GG_REQUIRE(which == 0 || which == 1, GG_ERR_VALUE, "which: 0 variance, 1 lengthscale");
+    GG_REQUIRE(dims >= 1 && x_dev && z_dev && out_dev && nx >= 0 && nz >= 0, GG_ERR_VALUE,
+               "bad argument");
+    const int64_t total = nx * nz;
+    if (total == 0) return;
+    const int nb = (int)std::min<int64_t>(8192, gg::ceil_div(total, 256));
+    hipLaunchKernelGGL(gg::cov_grad_param_kernel, dim3(nb), dim3(256), 0, gg::as_stream(stream),
+                       kind, variance, lengthscale, dims, x_dev, nx, z_dev, nz, which, out_dev);
     GG_LAUNCH_CHECK();
   });
 }

@@ -825,6 +825,108 @@ __global__ __launch_bounds__(kVecThreads) void logdet_kernel(KronDiag kd,
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
+// ---------------------------------------------- trace pass of the LML gradient
+// out[p] = sum_g prod_f num[p][off_f + g_f] / (prod_f lam[off_f + g_f] + shift).
+// A work item is (head index, segment of the last factor): the head -- every
+// factor but the last -- is decoded once per item, its eigenvalue product and
+// the kPC head numerators of this block's row chunk (blockIdx.y) stay in
+// registers, and the run over the segment is one FMA and one reciprocal per
+// grid point, shared by the kPC accumulators (a multiply and an FMA each).
+// No memory stream: the operands are the (P + 1) sum_f m_f table entries.
+// kIdx is uint32_t wherever N < 2^31 (the decode's divisions are the cost of
+// an item), int64_t beyond.  partials: P rows of gridDim.x.
+constexpr int kTraceRows = 8;    // rows of num per block (register accumulators)
+constexpr int kTraceSeg = 16;    // shortest segment worth a head decode
+constexpr int kTraceSegMax = 128;
+constexpr int64_t kTraceItems = 131072;  // items that fill the device
+
+template <int kPC, typename kIdx>
+__global__ __launch_bounds__(kVecThreads) void trace_ratio_kernel(
+    KronDiag kd, const double* __restrict__ lam, double shift, int P, int64_t rowlen,
+    const double* __restrict__ num, kIdx items, kIdx nseg, int seg,
+    double* __restrict__ partials) {
+  const int d = kd.d;
+  const int row0 = blockIdx.y * kPC;
+  const kIdx ml = (kIdx)kd.m[d - 1];
+  const int64_t offl = kd.off[d - 1];
+  // rows past P (the last chunk's tail) read row P - 1 and are never stored
+  const double* nrow[kPC];
+#pragma unroll
+  for (int q = 0; q < kPC; ++q) nrow[q] = num + (int64_t)min(row0 + q, P - 1) * rowlen;
+  double acc[kPC];
+#pragma unroll
+  for (int q = 0; q < kPC; ++q) acc[q] = 0.0;
+  const kIdx stride = (kIdx)gridDim.x * blockDim.x;
+  for (kIdx it = (kIdx)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+    kIdx hh = it / nseg;
+    const kIdx sg = it - hh * nseg;
+    double hl = 1.0;
+    double hn[kPC];
+#pragma unroll
+    for (int q = 0; q < kPC; ++q) hn[q] = 1.0;
+    for (int k = d - 2; k >= 0; --k) {
+      const kIdx mk = (kIdx)kd.m[k];
+      const kIdx nx = hh / mk;
+      const int64_t o = kd.off[k] + (int64_t)(hh - nx * mk);
+      hh = nx;
+      hl *= lam[o];
+#pragma unroll
+      for (int q = 0; q < kPC; ++q) hn[q] *= nrow[q][o];
+    }
+    const kIdx l0 = sg * (kIdx)seg;
+    const kIdx l1 = min(l0 + (kIdx)seg, ml);
+    for (kIdx l = l0; l < l1; ++l) {
+      const int64_t o = offl + (int64_t)l;
+      const double r = 1.0 / fma(hl, lam[o], shift);
+#pragma unroll
+      for (int q = 0; q < kPC; ++q) acc[q] = fma(hn[q] * nrow[q][o], r, acc[q]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kPC; ++q) {
+    const double s = block_sum(acc[q]);
+    __syncthreads();
+    if (threadIdx.x == 0 && row0 + q < P)
+      partials[(int64_t)(row0 + q) * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// out[blockIdx.x] = sum of row blockIdx.x of partials (rows of `count`)
+__global__ __launch_bounds__(1024) void reduce_rows_kernel(const double* __restrict__ partials,
+                                                           int64_t count,
+                                                           double* __restrict__ out) {
+  const double* row = partials + (int64_t)blockIdx.x * count;
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += row[i];
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+template <typename kIdx>
+static void launch_trace_ratio(int pc, dim3 grid, hipStream_t s, const KronDiag& kd,
+                               const double* lam, double shift, int P, int64_t rowlen,
+                               const double* num, int64_t items, int64_t nseg, int seg,
+                               double* partials) {
+#define GG_TRACE_CASE(PC)                                                                  \
+  case PC:                                                                                 \
+    hipLaunchKernelGGL((trace_ratio_kernel<PC, kIdx>), grid, dim3(kVecThreads), 0, s, kd,  \
+                       lam, shift, P, rowlen, num, (kIdx)items, (kIdx)nseg, seg, partials); \
+    break;
+  switch (pc) {
+    GG_TRACE_CASE(1)
+    GG_TRACE_CASE(2)
+    GG_TRACE_CASE(3)
+    GG_TRACE_CASE(4)
+    GG_TRACE_CASE(5)
+    GG_TRACE_CASE(6)
+    GG_TRACE_CASE(7)
+    default:
+      GG_TRACE_CASE(8)
+  }
+#undef GG_TRACE_CASE
+  GG_LAUNCH_CHECK();
+}
+
 static KronDiag make_diag(int d, const int64_t* m, int64_t* n_out) {
   GG_REQUIRE(d >= 1 && d <= 16, GG_ERR_VALUE, "1 <= d <= 16 factors supported");
   KronDiag kd{};
@@ -1076,6 +1178,50 @@ int gg_kron_logdet_shifted(int d, const int64_t* m, const double* lam_dev, doubl
     gg::launch_reduce_to(buf, nb, buf + gg::kVecBlocks, s);
     GG_HIP(hipMemcpyAsync(out_host, buf + gg::kVecBlocks, sizeof(double),
                           hipMemcpyDeviceToHost, s));
+    GG_HIP(hipFreeAsync(buf, s));
+    GG_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int gg_kron_trace_ratio(int d, const int64_t* m, const double* lam_dev, double shift, int P,
+                        const double* num_dev, double* out_host, gg_stream stream) {
+  return gg::guard([&] {
+    int64_t n = 0;
+    gg::KronDiag kd = gg::make_diag(d, m, &n);
+    GG_REQUIRE(P >= 0, GG_ERR_VALUE, "P must be >= 0");
+    GG_REQUIRE(lam_dev && num_dev && out_host, GG_ERR_VALUE, "NULL argument");
+    if (P == 0) return;
+    hipStream_t s = gg::as_stream(stream);
+    // items: (head, segment of the last factor).  Whole runs where the heads
+    // alone fill the device; shorter segments (never under kTraceSeg points,
+    // the decode's worth) on a grid with few heads, capped so that one
+    // thread's chain of additions stays short.
+    const int64_t ml = kd.m[d - 1], nhead = n / ml;
+    const int64_t want = gg::ceil_div(gg::kTraceItems, nhead);
+    int64_t seg = std::max(gg::ceil_div(ml, want), std::min<int64_t>(ml, gg::kTraceSeg));
+    seg = std::min<int64_t>(seg, gg::kTraceSegMax);
+    const int64_t nseg = gg::ceil_div(ml, seg), items = nhead * nseg;
+    const int nb = (int)std::min<int64_t>(gg::kVecBlocks, gg::ceil_div(items, gg::kVecThreads));
+    // P rows in equal chunks of at most kTraceRows, one chunk per blockIdx.y
+    const int nchunk = (P + gg::kTraceRows - 1) / gg::kTraceRows;
+    const int pc = (P + nchunk - 1) / nchunk;
+    GG_REQUIRE(nchunk <= 65535, GG_ERR_VALUE, "too many numerator rows");
+    int64_t rowlen = 0;
+    for (int k = 0; k < d; ++k) rowlen += kd.m[k];
+    double* buf = nullptr;
+    GG_HIP(hipMallocAsync(&buf, ((int64_t)P * nb + P) * sizeof(double), s));
+    double* out_dev = buf + (int64_t)P * nb;
+    const dim3 grid(nb, nchunk);
+    if (n < (int64_t(1) << 31))
+      gg::launch_trace_ratio<uint32_t>(pc, grid, s, kd, lam_dev, shift, P, rowlen, num_dev, items,
+                                       nseg, (int)seg, buf);
+    else
+      gg::launch_trace_ratio<int64_t>(pc, grid, s, kd, lam_dev, shift, P, rowlen, num_dev, items,
+                                      nseg, (int)seg, buf);
+    hipLaunchKernelGGL(gg::reduce_rows_kernel, dim3(P), dim3(1024), 0, s, buf, (int64_t)nb,
+                       out_dev);
+    GG_LAUNCH_CHECK();
+    GG_HIP(hipMemcpyAsync(out_host, out_dev, P * sizeof(double), hipMemcpyDeviceToHost, s));
     GG_HIP(hipFreeAsync(buf, s));
     GG_HIP(hipStreamSynchronize(s));
   });

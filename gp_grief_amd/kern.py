@@ -200,6 +200,32 @@ class Stationary(BaseKernel):
                                          zd.numel() // D, int(mode), native.dptr(out),
                                          native.stream_ptr()), "gg_cov")
 
+    def cov_grad_param(self, x, z=None):
+        """{'variance': d k / d variance, 'lengthscale': d k / d lengthscale},
+        each (N, M), on the device (gg_cov_grad_param); numpy in, numpy out
+        (CUDA tensors stay on device).  The reference has no counterpart: it
+        differentiates kernel parameters by finite differences."""
+        if self._children:
+            raise NotImplementedError("parameter gradients need a plain stationary kernel")
+        on_dev = dev.is_device_array(x)
+        x, z = self._process_cov_inputs(x, z)
+        xd, zd = [dev.to_device(v[:, self.active_dims.tolist()] if dev.is_device_array(v)
+                                else np.asarray(v, dtype=np.float64)[:, self.active_dims])
+                  for v in (x, z)]
+        D = int(self.active_dims.size)
+        N, M = int(x.shape[0]), int(z.shape[0])
+        out = {}
+        for which, name in enumerate(('variance', 'lengthscale')):
+            g = dev.empty(N * M)
+            native.check(native.lib().gg_cov_grad_param(
+                native.GG_KERN[self._kind], float(np.asarray(self.variance).reshape(-1)[0]),
+                float(np.asarray(self.lengthscale).reshape(-1)[0]), D, native.dptr(xd), N,
+                native.dptr(zd), M, which, native.dptr(g), native.stream_ptr()),
+                "gg_cov_grad_param")
+            g = g.reshape(N, M)
+            out[name] = g if on_dev else dev.to_host(g)
+        return out
+
     def _cov_into(self, x, z, out, mode=0, lengthscale=None):
         self._device_cov(x, z, mode, out, lengthscale)
         for op, child in self._children:
@@ -309,6 +335,33 @@ class GridKernel(object):
             assert not cross, "not implemented for cross covariances yet"
             K = K.sub_shift(shift=dim_noise_var)
         return K
+
+    def _check_grad_param(self):
+        """Raise unless cov_grid_grad covers this kernel."""
+        if self.radial_kernel:
+            raise NotImplementedError("cov_grid_grad: a radial kernel shares one parameter set "
+                                      "across the factors; not implemented")
+        for kern in self.kern_list:
+            if not isinstance(kern, Stationary) or kern._children:
+                raise NotImplementedError("cov_grid_grad needs plain stationary 1-D kernels, "
+                                          "not %s" % kern.name)
+            if list(kern.parameter_list) != ['variance', 'lengthscale']:
+                raise NotImplementedError("cov_grid_grad: unknown parameters of %s" % kern.name)
+
+    def cov_grid_grad(self, x, dim_noise_var=None):
+        """One entry per position of self.parameters, in its order: (factor
+        position in cov_grid's KronMatrix, d K_f / d theta as an m_f x m_f
+        array).  cov_grid reverses the dimensions, so dimension i sits at
+        position grid_dim - 1 - i; dim_noise_var is a constant added to the
+        factors and does not enter the derivative."""
+        self._check_grad_param()
+        assert len(x) == self.grid_dim
+        out = []
+        for i, kern in enumerate(self.kern_list):
+            g = kern.cov_grad_param(x=x[i])
+            for name in kern.parameter_list:
+                out.append((self.grid_dim - 1 - i, g[name]))
+        return out
 
     def cov(self, x, z=None, dim_noise_var=None):
         """Dense Hadamard product over dimensions (:118-145), on the device."""

@@ -18,6 +18,9 @@ Device solvers (no reference implementation exists):
                    Lanczos on (W K W + shift I) from probes zeroed at the
                    missing points (gg_lanczos_probe_masked), the estimator of
                    log det(K_oo + shift I) on an incomplete grid.
+  trace_grad    -- Hutchinson estimates of tr(A^-1) and tr(A^-1 dK) for the
+                   marginal likelihood's gradient, from the same masked probes
+                   as slq_logdet: one resident CG solve per probe.
 """
 import ctypes
 import logging
@@ -602,3 +605,63 @@ def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None):
         theta, U = np.linalg.eigh(T)
         ests.append(float(scale) * float(np.sum(U[0, :] ** 2 * np.log(theta))))
     return float(np.mean(ests)), np.array(ests)
+
+
+def trace_grad(K, dKs, shift, mask=None, probes=8, seed=0, rtol=1e-10, Z=None, solver=None):
+    """Probe estimates of the traces in the marginal likelihood's gradient:
+    (means, per_probe) with A = W K W + shift I, W = diag(mask) (the identity
+    without a mask).  per_probe is probes x (1 + len(dKs)): column 0 is
+    z^T A^-1 z (the noise's trace, tr A_oo^-1 in expectation), column 1 + k is
+    (A^-1 z)^T W dK_k W z (tr(A_oo^-1 dK_k,oo) in expectation); means is the
+    column mean.
+
+    dKs: KronMatrix operators (K with one factor replaced by its derivative).
+    Probe j is the Rademacher vector gg_probe_fill(seed, j) zeroed at the
+    missing points -- the vectors slq_logdet(mask=) starts from.  Z (N x k,
+    numpy or device) replaces them (probes = k; also zeroed at the missing
+    points): the unit vectors of the observed points give per-probe values that
+    sum to the exact traces.  Each probe is one solve on a resident
+    MaskedKronCG (KronCG without a mask) to rtol plus len(dKs) Kronecker
+    matvecs and dots; the vectors are reused across probes.  solver: a resident
+    MaskedKronCG / KronCG of (K, shift, mask) to solve with instead of a new
+    one (GPGridModel passes its own, with its preconditioner)."""
+    from . import dense
+    from . import device as dev
+    from . import native
+    n = int(K.shape[0])
+    t = dev.torch()
+    wd = None
+    if mask is not None:
+        if solver is None:
+            solver = MaskedKronCG(K, shift, mask)
+        wd = solver.mask.to(t.float64)
+    elif solver is None:
+        solver = KronCG(K, shift)
+    if Z is not None:
+        Zd = Z if dev.is_device_array(Z) else t.from_numpy(
+            np.ascontiguousarray(np.asarray(Z, dtype=np.float64))).to(dev.device())
+        if Zd.dim() != 2 or int(Zd.shape[0]) != n:
+            raise ValueError("Z must be (%d, k)" % n)
+        probes = int(Zd.shape[1])
+    maxiter = n * 10
+    check_every = 10 if n >= 1 << 20 else 50
+    z, x, w = dev.empty(n), dev.empty(n), dev.empty(n)
+    per = np.empty((int(probes), 1 + len(dKs)))
+    for j in range(int(probes)):
+        if Z is None:
+            native.check(native.lib().gg_probe_fill(int(seed), j, native.dptr(z), n,
+                                                    native.stream_ptr()), "gg_probe_fill")
+        else:
+            z.copy_(Zd[:, j])
+        if wd is not None:
+            dense.scale_rows(z, wd, 0)
+        solver.start(z, rtol, 0.0, x_out=x)
+        solver.iterate(maxiter, check_every=check_every)
+        it, conv = solver.status()[:2]
+        if not conv:
+            logger.info('trace_grad: probe %d did not converge in %d iterations' % (j, it))
+        per[j, 0] = dense.dot(z, x)
+        for k, dK in enumerate(dKs):
+            dK.matvec_device(z, out=w)
+            per[j, 1 + k] = dense.dot(x, w)
+    return per.mean(axis=0), per

@@ -25,6 +25,7 @@ Device state keeps the reference's attribute names (_Phi, _A, _P, _Pchol,
 _alpha, _alpha_p) holding CUDA tensors (or small host arrays where the
 reference keeps scalars/vectors).
 """
+import ctypes
 import logging
 from traceback import format_exc
 
@@ -684,9 +685,16 @@ class GPGridModel(BaseModel):
     and a decoded divide; the default on a complete grid) or 'cg' (device CG,
     linalg.KronCG; the default, and the only choice, with mask=).  logdet: 'exact'
     (streamed over the grid on the device) or 'slq' (with mask=: below).  Y (N,1) numpy or CUDA
-    tensor; results come back in the same kind.  grad_method is finite
-    differences over (noise, kernel parameters) like the reference's
-    kernel-parameter path.
+    tensor; results come back in the same kind.  grad_method:
+    'finite_difference' (the default; forward differences over (noise, kernel
+    parameters) like the reference's kernel-parameter path, one LML per free
+    parameter) or 'adjoint' -- the analytic gradient 1/2 alpha^T dK alpha -
+    1/2 tr((K + s I)^-1 dK) of one LML evaluation (_adjoint_gradient): on a
+    complete grid the traces are exact, streamed over the grid from the
+    per-factor eigenpairs (gg_kron_trace_ratio) whatever solver / logdet say;
+    with mask= they are Hutchinson estimates from grad_probes (default
+    slq_probes) masked probes, kept per probe in grad_estimates.  'adjoint'
+    needs plain stationary 1-D kernels (no radial_kernel, no composites).
 
     mask (bool / uint8, N entries, numpy or device; nonzero = observed): the
     grid with missing observations.  Y at the missing points is ignored (NaN
@@ -708,10 +716,19 @@ class GPGridModel(BaseModel):
 
     def __init__(self, xg, Y, kern, noise_var=1., solver=None, logdet='exact',
                  dim_noise_var=1e-12, cg_rtol=1e-10, slq_probes=8, slq_steps=50, seed=0,
-                 mask=None, precond=None, exact_missing_max=1024):
+                 mask=None, precond=None, exact_missing_max=1024,
+                 grad_method='finite_difference', grad_probes=None):
         super(GPGridModel, self).__init__()
         from .kern import GridKernel
         assert isinstance(kern, GridKernel)
+        if grad_method not in ('finite_difference', 'adjoint'):
+            raise ValueError("grad_method must be 'finite_difference' or 'adjoint'")
+        if grad_method == 'adjoint':
+            try:
+                kern._check_grad_param()
+            except NotImplementedError as e:
+                raise ValueError("grad_method='adjoint' needs a GridKernel of plain stationary "
+                                 "1-D kernels (%s); use grad_method='finite_difference'" % e)
         if solver is None:
             solver = 'exact' if mask is None else 'cg'
         if solver not in ('exact', 'cg'):
@@ -757,7 +774,9 @@ class GPGridModel(BaseModel):
             # Y at the missing points is never read again (it may be NaN)
             t = dev.torch()
             self._yd = t.where(self._mask != 0, self._yd, t.zeros_like(self._yd))
-        self.grad_method = 'finite_difference'
+        self.grad_method = grad_method
+        self.grad_probes = int(slq_probes if grad_probes is None else grad_probes)
+        self.grad_estimates = None
         self._K = self._QT = self._kern_key = None
         self.dependent_attributes = list(self.dependent_attributes)
         self._alpha = self._log_like = self._gradient = self._log_det = None
@@ -913,6 +932,81 @@ class GPGridModel(BaseModel):
         ll = -0.5 * (dense.dot(self._yd, self._alpha) + self._cov_log_det()
                      + self.num_observed * np.log(2 * np.pi))
         return np.array([[ll]])
+
+    def _adjoint_gradient(self, parameters):
+        """(LML, dL/d(noise, kernel parameters)) from
+        dL/dtheta = 1/2 alpha^T dK alpha - 1/2 tr((K + s I)^-1 dK), dK the
+        Kronecker operator with one factor replaced by its derivative
+        (GridKernel.cov_grid_grad; dK = I for the noise).
+
+        Complete grid: the traces are exact for every solver / logdet setting,
+        sum_g prod_f num_f[g_f] / (prod_f lam_f[g_f] + s) over the per-factor
+        eigenpairs K_f = Q_f lam_f Q_f^T with num_f = diag(Q_f^T dK_f Q_f) in the
+        parameter's factor and lam elsewhere (all ones for the noise): one
+        streamed device pass for all free parameters (gg_kron_trace_ratio).
+        mask=: Hutchinson estimates from grad_probes masked Rademacher probes
+        (linalg.trace_grad: the SLQ's probes, one masked CG solve each), their
+        per-probe values kept in grad_estimates (probes x (1 + kernel
+        parameters); column 0 the noise); the seed is fixed, so the gradient is
+        deterministic.  Entries of fixed parameters are 0."""
+        from . import native
+        from .linalg import trace_grad
+        from .tensors import KronMatrix
+        assert isinstance(parameters, np.ndarray)
+        log_like = self._compute_log_likelihood(parameters)
+        free = np.logical_not(self._fixed_indicies)
+        s = float(self.noise_var)
+        K = self._operator()
+        factors = list(K.K)
+        grads = self.kern.cov_grid_grad(self.xg, dim_noise_var=self.dim_noise_var)
+        assert len(grads) == parameters.size - 1
+        masked = self._mask is not None
+
+        def replaced(pos, dKf):
+            F = list(factors)
+            F[pos] = np.asarray(dKf, dtype=np.float64)
+            return KronMatrix(F, sym=True)
+
+        # kernel parameters whose operator is needed: the free ones (every one
+        # with mask=, where grad_estimates has a column per kernel parameter)
+        idx = [k for k in range(len(grads)) if masked or free[1 + k]]
+        ops = [replaced(*grads[k]) for k in idx]
+        alpha = self._alpha
+        fit_terms = np.zeros(parameters.shape)
+        fit_terms[0] = 0.5 * dense.dot(alpha, alpha)
+        w = dev.empty(self.num_data)
+        for k, op in zip(idx, ops):
+            op.matvec_device(alpha, out=w)
+            fit_terms[1 + k] = 0.5 * dense.dot(alpha, w)
+        traces = np.zeros(parameters.shape)
+        if masked:
+            means, self.grad_estimates = trace_grad(K, ops, s, mask=self._mask,
+                                                    probes=self.grad_probes, seed=self.slq[2],
+                                                    rtol=self.cg_rtol,
+                                                    solver=self._masked_cg())
+            traces[:] = means
+        else:
+            Q, T = self._schur()
+            lam = [np.asarray(e, dtype=np.float64).reshape(-1) for e in T.diag().K]
+            rows = [np.concatenate([np.ones_like(l) for l in lam])]
+            for k in idx:
+                pos, dKf = grads[k]
+                Qf = np.asarray(Q.K[pos], dtype=np.float64)
+                row = list(lam)
+                row[pos] = np.einsum('ij,ij->j', Qf, np.asarray(dKf, dtype=np.float64).dot(Qf))
+                rows.append(np.concatenate(row))
+            num = dev.to_device(np.concatenate(rows))
+            lamd = dev.to_device(np.concatenate(lam))
+            out = (ctypes.c_double * len(rows))()
+            native.check(native.lib().gg_kron_trace_ratio(
+                len(lam), native.i64_array([l.size for l in lam]), native.dptr(lamd), s,
+                len(rows), native.dptr(num), out, native.stream_ptr()), "gg_kron_trace_ratio")
+            traces[0] = out[0]
+            for j, k in enumerate(idx):
+                traces[1 + k] = out[1 + j]
+        gradient = fit_terms - 0.5 * traces
+        gradient[np.logical_not(free)] = 0.0
+        return log_like, gradient
 
     def _out(self, vd):
         return vd.reshape(-1, 1) if self._y_is_dev else dev.to_host(vd).reshape(-1, 1)

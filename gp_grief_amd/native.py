@@ -60,6 +60,8 @@ SIGNATURES = {
                            _c_dp, _vp],
     "gg_kron_logdet_shifted": [ctypes.c_int, _c_i64p, _c_dp, ctypes.c_double,
                                ctypes.POINTER(ctypes.c_double), _vp],
+    "gg_kron_trace_ratio": [ctypes.c_int, _c_i64p, _c_dp, ctypes.c_double, ctypes.c_int, _c_dp,
+                            ctypes.POINTER(ctypes.c_double), _vp],
     "gg_dot": [_c_dp, _c_dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), _vp],
     "gg_axpby": [ctypes.c_double, _c_dp, ctypes.c_double, _c_dp, ctypes.c_int64, _vp],
     "gg_scale_rows": [_c_dp, ctypes.c_int64, ctypes.c_int64, _c_dp, ctypes.c_int, _vp],
@@ -144,6 +146,8 @@ SIGNATURES = {
     "gg_centro_expand": [ctypes.c_int, _c_i64p, _c_i64p, _c_i64p, _c_dp, _c_dp, _vp],
     "gg_cov": [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_dp,
                ctypes.c_int64, _c_dp, ctypes.c_int64, ctypes.c_int, _c_dp, _vp],
+    "gg_cov_grad_param": [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_dp,
+                          ctypes.c_int64, _c_dp, ctypes.c_int64, ctypes.c_int, _c_dp, _vp],
     "gg_grief_tables": [ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_dp, ctypes.c_int64,
                         ctypes.c_int64, _c_dp, ctypes.c_int, _c_dp, ctypes.c_int, _c_dp, _c_dp,
                         ctypes.c_int, ctypes.c_int, _vp],

@@ -149,6 +149,22 @@ int gg_kron_diag_scale(int d, const int64_t* m, const double* lam_dev, double sh
  * Shifted generalisation of KronMatrix.log_det, kron_matrix.py:466-474.     */
 int gg_kron_logdet_shifted(int d, const int64_t* m, const double* lam_dev, double shift,
                            double* out_host, gg_stream stream);
+/* out_host[p] = sum over the whole grid of
+ *   prod_k num[p][off_k + i_k] / (prod_k lam_k[i_k] + shift),    p = 0 .. P - 1
+ * (synchronising): the traces tr((K + shift I)^-1 dK / d theta) of the marginal
+ * likelihood's gradient, from the per-factor eigenpairs K_k = Q_k lam_k Q_k^T.
+ * num_dev: P rows of sum_k m[k] doubles, each laid out like lam_dev; the row
+ * of a parameter of factor f holds diag(Q_f^T dK_f Q_f) in factor f and lam_k
+ * elsewhere, the noise's row is all ones.  One launch serves every row: the
+ * index is decoded once per run of the last factor, one reciprocal per grid
+ * point is shared by the rows, and nothing of order N is allocated.  The sums
+ * are per-block partials reduced by one block per row (no float atomics: the
+ * same input gives the same bits).  1 <= d <= 16; any P >= 0 (rows are taken
+ * in chunks of at most eight inside the one launch); P == 0 writes nothing and returns
+ * GG_OK.  GG_ERR_VALUE for P < 0 or a NULL pointer.  No reference counterpart
+ * (the reference's grid models have no analytic gradient).                   */
+int gg_kron_trace_ratio(int d, const int64_t* m, const double* lam_dev, double shift, int P,
+                        const double* num_dev, double* out_host, gg_stream stream);
 
 /* ------------------------------------------------- vector primitives (CG ops) */
 /* x . y (0 for n = 0); x and y at any 8-byte aligned address; synchronising. */
@@ -481,6 +497,16 @@ int gg_rows_orthonormalize(int count, const int64_t* k, const int64_t* m, double
 int gg_cov(int kind, double variance, double lengthscale, int dims, const double* x_dev,
            int64_t nx, const double* z_dev, int64_t nz, int mode, double* out_dev,
            gg_stream stream);
+/* out = d k(x_i, z_j) / d theta (nx x nz, written), arguments as gg_cov:
+ * which 0: theta = variance, k / variance (k at unit variance); which 1:
+ * theta = lengthscale l, with r = |x - z| / l: RBF k r^2 / l (0 under the
+ * l < 1e-6 delta rule), Exponential k r / l, Matern32 var 3 r^2 / l
+ * e^{-sqrt3 r}, Matern52 var (5 r^2 / 3 l)(1 + sqrt5 r) e^{-sqrt5 r}.  nx or
+ * nz == 0 writes nothing.  No reference counterpart (the reference
+ * differentiates its kernel parameters by finite differences).              */
+int gg_cov_grad_param(int kind, double variance, double lengthscale, int dims,
+                      const double* x_dev, int64_t nx, const double* z_dev, int64_t nz,
+                      int which, double* out_dev, gg_stream stream);
 /* Per-dimension tables of expand_SKC (gp_grief/tensors/tensors.py:97-128):
  * X[u][a] = sum_k qsel[u][k] k(xg[k], x[a * x_stride]); writes
  * ltab[a*U + col0 + u] = log|X| (0 where X == 0) and stab = sign(X), or with
