@@ -1118,15 +1118,20 @@ int gg_kron_create(int d, const int64_t* rows, const int64_t* cols,
   return gg::guard([&] {
     GG_REQUIRE(out != nullptr, GG_ERR_VALUE, "out is NULL");
     GG_REQUIRE(d >= 1, GG_ERR_VALUE, "need at least one factor");
+    GG_REQUIRE(rows != nullptr && cols != nullptr && factors_host != nullptr, GG_ERR_VALUE,
+               "NULL argument");
+    for (int k = 0; k < d; ++k) {
+      GG_REQUIRE(rows[k] >= 1 && cols[k] >= 1, GG_ERR_VALUE, "empty factor");
+      GG_REQUIRE(rows[k] <= (1 << 20) && cols[k] <= (1 << 20), GG_ERR_VALUE,
+                 "factor too large");
+      GG_REQUIRE(factors_host[k] != nullptr, GG_ERR_VALUE, "NULL factor");
+    }
     gg::knobs_reload();   // the handle's switches are the environment's now
     gg::set_lds_limits();
     gg_kron* K = new gg_kron();
     try {
       K->d = d;
       for (int k = 0; k < d; ++k) {
-        GG_REQUIRE(rows[k] >= 1 && cols[k] >= 1, GG_ERR_VALUE, "empty factor");
-        GG_REQUIRE(rows[k] <= (1 << 20) && cols[k] <= (1 << 20), GG_ERR_VALUE,
-                   "factor too large");
         K->n_rows *= rows[k];
         K->n_cols *= cols[k];
       }

@@ -929,6 +929,7 @@ static void launch_trace_ratio(int pc, dim3 grid, hipStream_t s, const KronDiag&
 
 static KronDiag make_diag(int d, const int64_t* m, int64_t* n_out) {
   GG_REQUIRE(d >= 1 && d <= 16, GG_ERR_VALUE, "1 <= d <= 16 factors supported");
+  GG_REQUIRE(m != nullptr, GG_ERR_VALUE, "NULL argument");
   KronDiag kd{};
   kd.d = d;
   int64_t n = 1, off = 0;
@@ -1386,6 +1387,9 @@ int gg_cg_create(const gg_kron* K, double shift, double* work_dev, gg_cg** out) 
       if (sized != t_cg_sized.end()) t_cg_sized.erase(sized);   // one check per sizing
       GG_REQUIRE((reinterpret_cast<uintptr_t>(work_dev) & 7) == 0, GG_ERR_VALUE,
                  "the CG workspace must hold doubles (8-byte aligned)");
+      // the caller's own alignment (the 256-byte round-up below would hide it):
+      // a base that is only 8-byte aligned takes the textbook recurrence
+      const bool base16 = (reinterpret_cast<uintptr_t>(work_dev) & 15) == 0;
       work_dev = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(work_dev) + 255) &
                                            ~static_cast<uintptr_t>(255));
       cg->r = work_dev;
@@ -1433,8 +1437,7 @@ int gg_cg_create(const gg_kron* K, double shift, double* work_dev, gg_cg** out) 
       GG_HIP(hipMalloc(&cg->partials, np * sizeof(double)));
       // the fused recurrence needs d >= 2 and 16-byte aligned vectors (its
       // side job moves double2); otherwise the textbook recurrence runs
-      cg->fused = gg::kron_d(K) >= 2 && (nr % 2) == 0 &&
-                  (reinterpret_cast<uintptr_t>(work_dev) & 15) == 0;
+      cg->fused = gg::kron_d(K) >= 2 && (nr % 2) == 0 && base16;
       if (cg->fused) {
         // capacity for any prologue launch shape; each iteration sums exactly
         // the partials its prologue launch wrote (MpFuse::pro_blocks)
@@ -1504,6 +1507,10 @@ int gg_cg_start(gg_cg* cg, const double* b_dev, double* x_dev, double rtol, doub
                "tolerances must be real, non-negative numbers");
     GG_REQUIRE(cg->rnblk < 0, GG_ERR_VALUE,
                "a block-range handle (gg_cg_create_blocks) runs through gg_cg_start_partial");
+    // the x / r update and the fused side job move x as 16-byte pairs
+    GG_REQUIRE((reinterpret_cast<uintptr_t>(x_dev) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(b_dev) & 7) == 0,
+               GG_ERR_VALUE, "x must be 16-byte aligned (b: 8-byte)");
     hipStream_t s = gg::as_stream(stream);
     cg->b = b_dev;
     cg->x = x_dev;
@@ -1522,6 +1529,10 @@ int gg_cg_start(gg_cg* cg, const double* b_dev, double* x_dev, double rtol, doub
       // r = P b (the fold, with its |P b|^2 partials), x_b = 0
       gg::block_fold(cg->blk, false, b_dev, cg->r, cg->partials, s);
       GG_HIP(hipMemsetAsync(cg->xb, 0, cg->nvec() * sizeof(double), s));
+      // the first prologue reads q_old with nothing pending; the fixed-count
+      // block kernel forms r - 0 * q_old there (no select), so whatever the
+      // caller's workspace held (a NaN, an Inf) must not be in q
+      GG_HIP(hipMemsetAsync(cg->q, 0, cg->nvec() * sizeof(double), s));
       hipLaunchKernelGGL(gg::cg_init_kernel, dim3(1), dim3(1024), 0, s, cg->partials,
                          gg::block_fold_partials(cg->blk), cg->sc, rtol, atol);
       GG_LAUNCH_CHECK();
@@ -1918,6 +1929,8 @@ int gg_cg_start_partial(gg_cg* cg, const double* b_dev, double* x_dev, double* r
     const int64_t n = cg->n;
     GG_HIP(hipMemcpyAsync(cg->r, b_dev, n * sizeof(double), hipMemcpyDeviceToDevice, s));
     GG_HIP(hipMemsetAsync(x_dev, 0, n * sizeof(double), s));
+    // as in gg_cg_start: the block prologue forms r - 0 * q_old on the first step
+    if (cg->block) GG_HIP(hipMemsetAsync(cg->q, 0, n * sizeof(double), s));
     const int nb = gg::vec_blocks(n);
     gg::launch_dot_partials(cg->r, cg->r, n, cg->partials, nb, s);
     gg::launch_reduce_to(cg->partials, nb, rr_dev, s);

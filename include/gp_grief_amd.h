@@ -55,7 +55,11 @@ int gg_device_synchronize(void);
 /* --------------------------------------------------- Kronecker operator (P1)
  * KronMatrix(K, sym)                    gp_grief/tensors/kron_matrix.py:19-42
  * factors_host[k] is a rows[k] x cols[k] row-major float64 matrix.  The handle
- * copies them to HBM in MFMA B-operand fragment order (for K and K^T).      */
+ * copies them to HBM in MFMA B-operand fragment order (for K and K^T).
+ * GG_ERR_VALUE, with *out untouched, for d < 1, a factor with no rows or
+ * columns or more than 2^20 of either, and for a NULL rows, cols,
+ * factors_host, factors_host[k] or out (all checked before anything is read).
+ * gg_kron_destroy(NULL) is GG_OK.                                            */
 int gg_kron_create(int d, const int64_t* rows, const int64_t* cols,
                    const double* const* factors_host, gg_kron** out);
 int gg_kron_destroy(gg_kron* K);
@@ -74,7 +78,13 @@ int gg_kron_fold_mask(const gg_kron* K, int transpose, int64_t* mask);
 
 /* y = (K_0 (x) ... (x) K_{d-1})^{T?} x + shift * x
  * KronMatrix.kronvec_prod / __mul__ / .T     kron_matrix.py:52-102, 203-213
- * (shift != 0 needs a square operator; x and y must not alias).            */
+ * (shift != 0 needs a square operator; x and y must not alias).  x, y and
+ * work_dev at any 8-byte aligned address (16-byte aligned operands may take
+ * kernels that move pairs; the result's accuracy does not depend on it).
+ * work_dev: exactly gg_kron_shape's work_elems doubles are used, none is read
+ * before it is written; NULL is accepted for d == 1 only.  Refused with
+ * GG_ERR_VALUE before any launch: x_dev == y_dev, a shift on a non-square
+ * operator, a NULL pointer.                                                 */
 int gg_kron_matvec(const gg_kron* K, int transpose, const double* x_dev, double* y_dev,
                    double shift, double* work_dev, gg_stream stream);
 /* reps back-to-back gg_kron_matvec calls with HIP events around every mode
@@ -138,7 +148,9 @@ int gg_kron_block_matvec_timed(const gg_kron* K, const double* x_dev, double* y_
 
 /* y = x / (prod_k lam_k[i_k] + shift), the eigenvalue product decoded from
  * the flat index on the fly (never expanded).  solve_schur's divide,
- * kron_matrix.py:349-350.  lam_dev: concatenated per-factor eigenvalues.   */
+ * kron_matrix.py:349-350.  lam_dev: concatenated per-factor eigenvalues.
+ * 1 <= d <= 16 and every m[k] >= 1, else GG_ERR_VALUE -- as for a NULL m (for
+ * gg_kron_logdet_shifted and gg_kron_trace_ratio too).                       */
 int gg_kron_diag_scale(int d, const int64_t* m, const double* lam_dev, double shift,
                        int mode, const double* x_dev, double* y_dev, gg_stream stream);
 #define GG_DIAG_DIVIDE 0   /* y = x / (t + shift)            */
@@ -193,7 +205,19 @@ int gg_diag_divide(const double* t_dev, double shift, const double* x_dev, doubl
  *     drives the stopping test and alpha) -- same iterates as scipy's up to
  *     rounding;
  *   textbook (0): scipy's operation order (separate x / r update pass).
- * Either way gg_cg_iterate returns in the textbook state (x_k, r_k, k).     */
+ * Either way gg_cg_iterate returns in the textbook state (x_k, r_k, k).
+ * Alignment: work_dev at any 8-byte aligned address, but the fused recurrence
+ * (and with it the block basis) is only chosen for a 16-byte aligned work_dev
+ * and an even n -- otherwise the handle runs the textbook recurrence
+ * (gg_cg_get_recurrence reports it) and gg_cg_set_recurrence(1) is refused.
+ * x_dev must be 16-byte aligned in either recurrence (the update kernels move
+ * x in pairs), b_dev 8-byte; gg_cg_start returns GG_ERR_VALUE otherwise, as
+ * for a negative or NaN rtol / atol, before anything is written.  gg_cg_start
+ * may be called again on a started handle (a new solve, the same bits as on
+ * a fresh handle); every gg_cg_set_* after the first start is GG_ERR_VALUE.
+ * gg_cg_iterate: max_iters == 0 does nothing (GG_OK); check_every <= 0 never
+ * polls -- the device's own done flag stops the recurrence at the same
+ * iteration, with the same x, as polling every iteration does.              */
 int gg_cg_work_elems(const gg_kron* K, int64_t* elems);
 int gg_cg_create(const gg_kron* K, double shift, double* work_dev, gg_cg** out);
 int gg_cg_destroy(gg_cg* cg);
@@ -378,7 +402,20 @@ int gg_cgm_status(gg_cgm* cgm, int* iters, int* converged, double* resid_norm, d
  * k steps of three-term Lanczos on (K + shift I) from z / ||z|| where z is the
  * Rademacher probe (seed, probe) (oracle/cg.py probe_signs).  Writes the
  * tridiagonal (alphas[k], betas[k]) to host memory (synchronising).
- * work_dev: 4 * n elements.                                                   */
+ * work_dev: 4 * n elements (all of them scratch: nothing is read before it is
+ * written).  All `steps` entries of both arrays are always written and
+ * finite: betas[j] = |w_j| is the norm of step j's residual, so T_k uses
+ * alphas[0 .. k-1] and betas[0 .. k-2].  *steps_done (may be NULL) = k: steps,
+ * or j + 1 for the first j with betas[j] == 0 (an exact breakdown: the Krylov
+ * space is invariant; the later entries are then zeros, not part of T).  A
+ * beta that merely falls to rounding level (the space exhausted in floating
+ * point, e.g. steps beyond the number of distinct eigenvalues or beyond n)
+ * does not stop the count: the steps that follow restart from rounding noise,
+ * their Ritz values stay inside the spectrum and their quadrature weights
+ * U[0][j]^2 are of the order of that beta squared, so n sum U[0]^2 log theta
+ * is unchanged.  GG_ERR_VALUE before any launch, the host arrays untouched:
+ * steps < 1, a non-square operator or non-square factors, a NULL K, work_dev,
+ * alphas_host or betas_host.                                                 */
 int gg_lanczos_probe(const gg_kron* K, double shift, uint64_t seed, int probe, int steps,
                      double* work_dev, double* alphas_host, double* betas_host,
                      int* steps_done, gg_stream stream);
