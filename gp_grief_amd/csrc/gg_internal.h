@@ -228,7 +228,40 @@ inline int vec_blocks(int64_t n) {
   return (int)std::min<int64_t>(kVecBlocks, std::max<int64_t>(want, 1));
 }
 
+// ---- Kronecker eigenvalue diagonal: the factor orders and each factor's
+// offset into the concatenated eigenvalue table (gg_vec.hip, gg_sample.hip)
+struct KronDiag {
+  int d;
+  int64_t m[16];
+  int64_t off[16];
+};
+
+inline KronDiag make_diag(int d, const int64_t* m, int64_t* n_out) {
+  GG_REQUIRE(d >= 1 && d <= 16, GG_ERR_VALUE, "1 <= d <= 16 factors supported");
+  GG_REQUIRE(m != nullptr, GG_ERR_VALUE, "NULL argument");
+  KronDiag kd{};
+  kd.d = d;
+  int64_t n = 1, off = 0;
+  for (int k = 0; k < d; ++k) {
+    GG_REQUIRE(m[k] >= 1, GG_ERR_VALUE, "empty factor");
+    kd.m[k] = m[k];
+    kd.off[k] = off;
+    off += m[k];
+    n *= m[k];
+  }
+  *n_out = n;
+  return kd;
+}
+
 #if defined(__HIPCC__)
+// splitmix64's finaliser: the counter-based hash of the Rademacher probes
+// (gg_vec.hip) and of the Gaussian stream (gg_sample.hip)
+__device__ __forceinline__ uint64_t probe_mix(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

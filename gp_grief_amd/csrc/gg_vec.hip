@@ -740,13 +740,8 @@ __global__ __launch_bounds__(kVecThreads) void diag_divide_kernel(const double* 
     y[i] = x[i] / (t[i] + shift);
 }
 
-// Rademacher probe, bit-identical to oracle/cg.py probe_signs (splitmix64)
-__device__ __forceinline__ uint64_t probe_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
+// Rademacher probe, bit-identical to oracle/cg.py probe_signs (splitmix64;
+// probe_mix: gg_internal.h)
 __global__ __launch_bounds__(kVecThreads) void probe_kernel(uint64_t base, double scale,
                                                             double* __restrict__ z, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -762,12 +757,7 @@ static uint64_t probe_base(uint64_t seed, int probe) {
 }
 
 // ----------------------------------------------- Kronecker eigenvalue diagonal
-struct KronDiag {
-  int d;
-  int64_t m[16];
-  int64_t off[16];
-};
-
+// (KronDiag, make_diag: gg_internal.h, shared with gg_sample.hip)
 __device__ __forceinline__ double kron_eig_at(const KronDiag& kd, const double* lam, int64_t i) {
   double t = 1.0;
   for (int k = kd.d - 1; k >= 0; --k) {
@@ -925,23 +915,6 @@ static void launch_trace_ratio(int pc, dim3 grid, hipStream_t s, const KronDiag&
   }
 #undef GG_TRACE_CASE
   GG_LAUNCH_CHECK();
-}
-
-static KronDiag make_diag(int d, const int64_t* m, int64_t* n_out) {
-  GG_REQUIRE(d >= 1 && d <= 16, GG_ERR_VALUE, "1 <= d <= 16 factors supported");
-  GG_REQUIRE(m != nullptr, GG_ERR_VALUE, "NULL argument");
-  KronDiag kd{};
-  kd.d = d;
-  int64_t n = 1, off = 0;
-  for (int k = 0; k < d; ++k) {
-    GG_REQUIRE(m[k] >= 1, GG_ERR_VALUE, "empty factor");
-    kd.m[k] = m[k];
-    kd.off[k] = off;
-    off += m[k];
-    n *= m[k];
-  }
-  *n_out = n;
-  return kd;
 }
 
 }  // namespace gg

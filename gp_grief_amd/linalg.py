@@ -21,6 +21,10 @@ Device solvers (no reference implementation exists):
   trace_grad    -- Hutchinson estimates of tr(A^-1) and tr(A^-1 dK) for the
                    marginal likelihood's gradient, from the same masked probes
                    as slq_logdet: one resident CG solve per probe.
+  GridPosteriorSampler -- joint draws of the latent field's posterior on the
+                   grid (gg_sample.hip): one Kronecker matvec per draw in the
+                   eigenbasis on a complete grid, Matheron's rule (one CG
+                   solve per draw) with a mask or the CG solver.
 """
 import ctypes
 import logging
@@ -665,3 +669,162 @@ def trace_grad(K, dKs, shift, mask=None, probes=8, seed=0, rtol=1e-10, Z=None, s
             dK.matvec_device(z, out=w)
             per[j, 1 + k] = dense.dot(x, w)
     return per.mean(axis=0), per
+
+
+class GridPosteriorSampler(object):
+    """Joint draws of the posterior of the latent field f at all N grid points,
+    y = f + noise observed with variance `shift` on the whole grid or, with
+    mask=, on its observed points.
+
+    Draw k is a function of (seed, k) alone: its normals are streams 2k (the
+    prior / eigenbasis normals) and 2k + 1 (the noise normals) of
+    gg_normal_fill's counter-based generator, regenerated inside the fused
+    passes and never stored, so k < 32768.  Three routes:
+
+      complete grid, solver='exact' (the default without a mask): the posterior
+        is diagonal in the eigenbasis K = Q diag(t) Q^T; c = t / (t + s) Q^T y +
+        sqrt(t s / (t + s)) z (gg_kron_posterior_coeffs) and the draw is Q c --
+        one streaming pass and one Kronecker matvec, exactly Gaussian.
+      complete grid, solver='cg': Matheron's rule in grid space.  f = Q (sqrt(t)
+        z) is a prior draw (gg_kron_prior_coeffs), b = y - f - sqrt(s) e
+        (gg_sample_residual), alpha = (K + s I)^-1 b by linalg.cg's resident
+        solver (KronCG), and the draw is f + K alpha (gg_sample_accumulate).
+      mask=: the same with b zeroed at the missing points and alpha from
+        MaskedKronCG (masked_cg: a resident solver of (K, shift, mask) to
+        reuse, e.g. the model's; else one is made with precond).
+
+    y_dev: N doubles on the device (at the missing points it is not read: NaN
+    allowed).  rtol: the CG's relative tolerance.  schur: (Q, T) of K.schur()
+    to reuse.  The work vectors (three of N doubles, two in the eigenbasis
+    route besides Q^T y) are held across draws.
+    """
+
+    MAX_DRAWS = 32768
+
+    def __init__(self, K, shift, y_dev, mask=None, solver=None, precond=None, rtol=1e-10,
+                 seed=0, masked_cg=None, schur=None):
+        from . import device as dev
+        from . import native
+        if solver is None:
+            solver = 'exact' if mask is None and masked_cg is None else 'cg'
+        if solver not in ('exact', 'cg'):
+            raise ValueError("solver must be 'exact' or 'cg'")
+        masked = mask is not None or masked_cg is not None
+        if masked and solver == 'exact':
+            raise ValueError("mask=: solver='exact' does not apply to an incomplete grid; "
+                             "use solver='cg'")
+        if precond is not None and not masked:
+            raise ValueError("precond= needs mask=")
+        self.K = K
+        self.shift = float(shift)
+        if not self.shift > 0.0:
+            raise ValueError("shift (the noise variance) must be positive")
+        self.n = int(K.shape[0])
+        self.rtol = float(rtol)
+        self.seed = int(seed)
+        self.y = dev.ensure_aligned(dev.to_device(y_dev))
+        if self.y.numel() != self.n:
+            raise ValueError("y must have %d entries" % self.n)
+        self.Q, T = K.schur() if schur is None else schur
+        lam = [np.asarray(e, dtype=np.float64).reshape(-1) for e in T.diag().K]
+        self._d = len(lam)
+        self._ms = native.i64_array([l.size for l in lam])
+        self._lam = dev.to_device(np.concatenate(lam))
+        self.mask = self._cg = None
+        if masked:
+            self.route = 'matheron'
+            self._cg = masked_cg if masked_cg is not None else \
+                MaskedKronCG(K, self.shift, mask, precond=precond)
+            if self._cg.n != self.n or self._cg.shift != self.shift:
+                raise ValueError("masked_cg solves another system")
+            self.mask = self._cg.mask
+        elif solver == 'cg':
+            self.route = 'matheron'
+            self._cg = KronCG(K, self.shift)
+        else:
+            self.route = 'eigen'
+            self._yt = self.Q.matvec_device(self.y, transpose=True)
+        self._c = dev.empty(self.n)          # coefficients, then b, then K alpha
+        self._f = dev.empty(self.n)          # the prior draw (eigen route: the draw)
+        self._alpha = dev.empty(self.n) if self.route == 'matheron' else None
+        self.cg_iters = []
+
+    def _streams(self, k):
+        k = int(k)
+        if k < 0 or k >= self.MAX_DRAWS:
+            raise ValueError("draw index must be in [0, %d): draw k uses streams 2k and 2k + 1 "
+                             "of 65536" % self.MAX_DRAWS)
+        return 2 * k, 2 * k + 1
+
+    def _terms(self, k):
+        """(f, w) with draw k = f + w; w is None in the eigenbasis route."""
+        from . import native
+        L, sp = native.lib(), native.stream_ptr
+        s0, s1 = self._streams(k)
+        if self.route == 'eigen':
+            native.check(L.gg_kron_posterior_coeffs(
+                self._d, self._ms, native.dptr(self._lam), self.shift, native.dptr(self._yt),
+                self.seed, s0, native.dptr(self._c), sp()), "gg_kron_posterior_coeffs")
+            self.Q.matvec_device(self._c, out=self._f)
+            return self._f, None
+        native.check(L.gg_kron_prior_coeffs(
+            self._d, self._ms, native.dptr(self._lam), self.seed, s0, native.dptr(self._c),
+            sp()), "gg_kron_prior_coeffs")
+        self.Q.matvec_device(self._c, out=self._f)
+        mp = None if self.mask is None else ctypes.c_void_p(self.mask.data_ptr())
+        native.check(L.gg_sample_residual(
+            native.dptr(self.y), native.dptr(self._f), mp, float(np.sqrt(self.shift)),
+            self.seed, s1, native.dptr(self._c), self.n, sp()), "gg_sample_residual")
+        cg_ = self._cg
+        cg_.start(self._c, self.rtol, 0.0, x_out=self._alpha)
+        cg_.iterate(self.n * 10, check_every=10 if self.n >= 1 << 20 else 50)
+        it, conv = cg_.status()[:2]
+        if not conv:
+            logger.info('posterior draw %d: CG did not converge in %d iterations' % (k, it))
+        self.cg_iters.append(it)
+        # the solve is over: its right-hand side's buffer takes K alpha
+        self.K.matvec_device(self._alpha, out=self._c)
+        return self._f, self._c
+
+    def draw(self, k, out=None):
+        """Draw k (N doubles on the device; into out when given)."""
+        from . import device as dev
+        from . import native
+        if out is not None and (out.numel() != self.n or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous device vector of %d entries" % self.n)
+        f, w = self._terms(k)
+        if w is None:
+            if out is None:
+                return f.clone()
+            out.reshape(-1).copy_(f)
+            return out
+        x = dev.empty(self.n) if out is None else out
+        native.check(native.lib().gg_sample_accumulate(
+            native.dptr(f), native.dptr(w), native.dptr(x), None, None, 0, self.n,
+            native.stream_ptr()), "gg_sample_accumulate")
+        return x
+
+    def moments(self, n_samples):
+        """(mean, var) of draws 0 .. n_samples - 1, each N doubles on the device:
+        the sample mean and the unbiased sample variance, streamed through
+        Welford's update (gg_sample_accumulate) without keeping a draw."""
+        from . import device as dev
+        from . import native
+        S = int(n_samples)
+        if S < 2:
+            raise ValueError("the sample variance needs n_samples >= 2")
+        self._streams(S - 1)
+        mean, m2 = dev.empty(self.n), dev.empty(self.n)
+        scale = 1.0
+        for k in range(S):
+            f, w = self._terms(k)
+            if w is None:
+                # the eigenbasis draw has one term: fold x + x and halve at the
+                # end (scaling by two is exact in every step of the update)
+                w, scale = f, 0.5
+            native.check(native.lib().gg_sample_accumulate(
+                native.dptr(f), native.dptr(w), None, native.dptr(mean), native.dptr(m2), k + 1,
+                self.n, native.stream_ptr()), "gg_sample_accumulate")
+        mean *= scale
+        m2 *= scale * scale / (S - 1)
+        return mean, m2

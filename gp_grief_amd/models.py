@@ -712,6 +712,12 @@ class GPGridModel(BaseModel):
     linalg.slq_logdet(mask=)): the one choice that is an estimator of the log
     det at any number of missing points, its per-probe estimates kept in
     slq_estimates.
+
+    sample_posterior(n_samples, seed) / posterior_moments(n_samples, seed):
+    joint draws of the latent field's posterior at all N grid points (missing
+    ones included) and their streamed mean / variance -- one Kronecker matvec
+    per draw with solver='exact', one (masked) CG solve per draw otherwise
+    (linalg.GridPosteriorSampler).
     """
 
     def __init__(self, xg, Y, kern, noise_var=1., solver=None, logdet='exact',
@@ -778,6 +784,7 @@ class GPGridModel(BaseModel):
         self.grad_probes = int(slq_probes if grad_probes is None else grad_probes)
         self.grad_estimates = None
         self._K = self._QT = self._kern_key = None
+        self._sampler_obj = self._sampler_key = None
         self.dependent_attributes = list(self.dependent_attributes)
         self._alpha = self._log_like = self._gradient = self._log_det = None
 
@@ -1038,6 +1045,53 @@ class GPGridModel(BaseModel):
         Q2 = KronMatrix([np.asarray(q) ** 2 for q in Q.K])
         var = Q2.matvec_device(v)
         var += s
+        return self._out(mean), self._out(var)
+
+    def _sampler(self, seed):
+        """The resident posterior sampler, cached on (kernel parameters, noise)
+        like the masked solver (which it shares)."""
+        from .linalg import GridPosteriorSampler
+        self.parameters
+        K = self._operator()
+        key = (id(K), float(self.noise_var))
+        if self._sampler_obj is None or self._sampler_key != key:
+            self._sampler_obj = GridPosteriorSampler(
+                K, float(self.noise_var), self._yd, solver=self.solver, rtol=self.cg_rtol,
+                masked_cg=self._masked_cg() if self._mask is not None else None,
+                schur=self._schur())
+            self._sampler_key = key
+        self._sampler_obj.seed = int(self.slq[2] if seed is None else seed)
+        return self._sampler_obj
+
+    def sample_posterior(self, n_samples=1, seed=None):
+        """(N, n_samples) joint draws of the latent field's posterior at all N
+        grid points, the missing ones included (linalg.GridPosteriorSampler:
+        one Kronecker matvec per draw with solver='exact', one CG solve per
+        draw by Matheron's rule with solver='cg' or mask=).  Column k is draw k
+        of `seed` (default: the model's seed): the same whatever n_samples.
+        numpy or a device tensor, as Y was (on the device the result is the
+        transposed view of n_samples contiguous draws).  Add noise of variance
+        noise_var for draws of new observations."""
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be >= 1")
+        smp = self._sampler(seed)
+        smp._streams(S - 1)
+        t = dev.torch()
+        rows = t.empty((S, self.num_data), dtype=t.float64, device=self._yd.device)
+        for k in range(S):
+            smp.draw(k, out=rows[k])
+        if self._y_is_dev:
+            return rows.t()
+        return np.ascontiguousarray(dev.to_host(rows).T)
+
+    def posterior_moments(self, n_samples, seed=None):
+        """(mean, var), each (N, 1): the sample mean and the unbiased sample
+        variance of the latent field over draws 0 .. n_samples - 1 of `seed`
+        -- the moments of sample_posterior(n_samples, seed) -- streamed on the
+        device without keeping a draw.  var is the latent variance: add
+        noise_var for the predictive variance of a new observation."""
+        mean, var = self._sampler(seed).moments(n_samples)
         return self._out(mean), self._out(var)
 
     def predict(self, Xnew, compute_var=True):

@@ -134,6 +134,15 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int), _c_i64p,
                                       ctypes.POINTER(ctypes.c_double), _vp],
     "gg_probe_fill": [ctypes.c_uint64, ctypes.c_int, _c_dp, ctypes.c_int64, _vp],
+    "gg_normal_fill": [ctypes.c_uint64, ctypes.c_int, _c_dp, ctypes.c_int64, _vp],
+    "gg_kron_posterior_coeffs": [ctypes.c_int, _c_i64p, _c_dp, ctypes.c_double, _c_dp,
+                                 ctypes.c_uint64, ctypes.c_int, _c_dp, _vp],
+    "gg_kron_prior_coeffs": [ctypes.c_int, _c_i64p, _c_dp, ctypes.c_uint64, ctypes.c_int, _c_dp,
+                             _vp],
+    "gg_sample_residual": [_c_dp, _c_dp, _vp, ctypes.c_double, ctypes.c_uint64, ctypes.c_int,
+                           _c_dp, ctypes.c_int64, _vp],
+    "gg_sample_accumulate": [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int64,
+                             _vp],
     "gg_sym_eig_batched": [ctypes.c_int, _c_i64p, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
                            ctypes.c_int, _vp],
     "gg_sym_eig_work_elems": [ctypes.c_int, _c_i64p, _c_i64p],

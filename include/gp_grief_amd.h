@@ -476,6 +476,60 @@ int gg_lanczos_probe_masked_timed(const gg_kron* K, double shift, const uint8_t*
                                   gg_stream stream);
 int gg_probe_fill(uint64_t seed, int probe, double* z_dev, int64_t n, gg_stream stream);
 
+/* ------------------------------------ posterior sampling
+ * z[0 .. n-1] = standard normals of the counter-based stream (seed, stream):
+ * element i depends on (seed, stream, i) alone, so the vector does not depend
+ * on the launch shape and the fused passes below regenerate it instead of
+ * reading it.  With all integer arithmetic mod 2^64,
+ *   base = ((seed & 0xffffffff) << 32) ^ ((stream & 0xffff) << 16)
+ *          ^ 0xD1B54A32D192ED03          (not the probes' constant: the two
+ *                                         families never share a stream)
+ *   h(i) = splitmix64's finaliser of base + i * 0x9E3779B97F4A7C15
+ *          (the hash of gg_probe_fill),
+ * and for pair j (Box-Muller)
+ *   u1 = ((h(2j) >> 11) + 1) 2^-53 in (0, 1],  u2 = (h(2j+1) >> 11) 2^-53 in [0, 1),
+ *   r = sqrt(-2 ln u1),  z[2j] = r cos(2 pi u2),  z[2j+1] = r sin(2 pi u2);
+ * an odd n takes the cosine half of its last pair.  |z| <= 8.6.  z_dev at any
+ * 8-byte aligned address (16-byte: one store per pair).  n == 0 is a no-op;
+ * GG_ERR_VALUE, z untouched, for a NULL z_dev, n < 0 or stream outside
+ * [0, 65535].  No reference counterpart (the reference draws no sample).     */
+int gg_normal_fill(uint64_t seed, int stream, double* z_dev, int64_t n, gg_stream s);
+/* The posterior of the latent field on a complete grid is diagonal in the
+ * eigenbasis K = Q diag(t) Q^T: with yt = Q^T y,
+ *   c[i] = t / (t + shift) yt[i] + sqrt(max(t, 0) shift / (t + shift)) z[i],
+ * t the Kronecker eigenvalue of element i decoded from the concatenated
+ * per-factor eigenvalues lam_dev (as gg_kron_diag_scale; the head once per
+ * pair of elements) and z the stream (seed, stream) above, generated in the
+ * kernel and never stored: one read and one write pass.  The draw is Q c, one
+ * Kronecker matvec.  c_dev may be yt_dev (element-wise).  GG_ERR_VALUE, c
+ * untouched: d outside 1..16, a NULL m or a zero order, a NULL lam_dev, yt_dev
+ * or c_dev, shift <= 0, stream outside [0, 65535].                           */
+int gg_kron_posterior_coeffs(int d, const int64_t* m, const double* lam_dev, double shift,
+                             const double* yt_dev, uint64_t seed, int stream, double* c_dev,
+                             gg_stream s);
+/* c[i] = sqrt(max(t, 0)) z[i] (write only): Q c is a draw of the prior
+ * N(0, K).  Refusals as gg_kron_posterior_coeffs (no shift, no yt).          */
+int gg_kron_prior_coeffs(int d, const int64_t* m, const double* lam_dev, uint64_t seed,
+                         int stream, double* c_dev, gg_stream s);
+/* Matheron's rule, the right-hand side: b[i] = y[i] - f[i] - noise_sd z[i]
+ * where mask_dev[i] != 0 (everywhere for a NULL mask) and exactly 0 elsewhere
+ * -- a select, so a NaN in y at a missing point does not reach b.  f: a prior
+ * draw, z: the stream (seed, stream).  mask_dev: n bytes, any alignment.
+ * n == 0 is a no-op; GG_ERR_VALUE, b untouched: a NULL y_dev, f_dev or b_dev,
+ * n < 0, stream outside [0, 65535].                                          */
+int gg_sample_residual(const double* y_dev, const double* f_dev, const uint8_t* mask_dev,
+                       double noise_sd, uint64_t seed, int stream, double* b_dev, int64_t n,
+                       gg_stream s);
+/* x = f + w (Matheron: the prior draw plus K alpha), stored to out_dev (may be
+ * NULL, or f_dev / w_dev themselves) and folded into Welford's running moments
+ * as draw number k = 1, 2, .. (mean_dev, m2_dev: both given or both NULL;
+ * k == 1 initialises them, so they need not be cleared): after k draws mean is
+ * the sample mean and m2 / (k - 1) the unbiased sample variance.  One pass.
+ * GG_ERR_VALUE, nothing written: a NULL f_dev or w_dev, n < 0, one of mean_dev
+ * / m2_dev without the other, k < 1 with moments.                            */
+int gg_sample_accumulate(const double* f_dev, const double* w_dev, double* out_dev,
+                         double* mean_dev, double* m2_dev, int k, int64_t n, gg_stream s);
+
 /* --------------------------------------- per-factor symmetric eigensolver
  * KronMatrix.schur / svd / eig_vals per factor   kron_matrix.py:161-200, 355-366
  * Householder tridiagonalisation + implicit QL on device, one workgroup per
