@@ -26,16 +26,6 @@
 
 namespace gg {
 
-// defined in gg_kron.hip
-void kron_apply(const gg_kron* K, bool transpose, const double* x, double* y, double shift,
-                double* work, double* dot_partials, const int* skip, hipStream_t stream,
-                int64_t* n_partials_out, const MpFuse* cg, int cgp, hipEvent_t* ev);
-int64_t kron_partials_needed(const gg_kron* K, bool transpose);
-int64_t kron_work_elems(const gg_kron* K, bool transpose);
-int64_t kron_n(const gg_kron* K);
-int kron_d(const gg_kron* K);
-void kron_factor_shape(const gg_kron* K, int64_t* rows, int64_t* cols);
-
 // the masked CG's device scalars
 struct CgmScalars {
   double rho;       // r.z (r.r unpreconditioned) of the current residual
@@ -50,8 +40,6 @@ struct CgmScalars {
   int done;         // 1 = converged / stopped: every kernel becomes a no-op
   int first;        // 1 = the next direction is p = u
 };
-
-__device__ __forceinline__ double sel(uint8_t m, double v) { return m ? v : 0.0; }
 
 // r = select(mask, b, 0) ; x = 0 ; partial r.r
 template <bool V2>
@@ -177,9 +165,7 @@ __global__ __launch_bounds__(kVecThreads) void cgm_direction_kernel(
 __global__ __launch_bounds__(1024) void cgm_init_kernel(const double* __restrict__ partials,
                                                         int64_t count, CgmScalars* sc,
                                                         double rtol, double atol) {
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     sc->rho = s;
     sc->rho_prev = 0.0;
@@ -197,9 +183,7 @@ __global__ __launch_bounds__(1024) void cgm_init_kernel(const double* __restrict
 __global__ __launch_bounds__(1024) void cgm_alpha_kernel(const double* __restrict__ partials,
                                                          int64_t count, CgmScalars* sc) {
   if (sc->done) return;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     sc->pq = s;
     sc->alpha = sc->rho / s;
@@ -213,9 +197,7 @@ __global__ __launch_bounds__(1024) void cgm_rr_kernel(const double* __restrict__
                                                       int64_t count, CgmScalars* sc,
                                                       int precond) {
   if (sc->done) return;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     sc->rr = s;
     if (!precond) {
@@ -233,9 +215,7 @@ __global__ __launch_bounds__(1024) void cgm_rr_kernel(const double* __restrict__
 __global__ __launch_bounds__(1024) void cgm_rz_kernel(const double* __restrict__ partials,
                                                       int64_t count, CgmScalars* sc, int init) {
   if (sc->done) return;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     if (init) {
       sc->rho = s;
@@ -245,16 +225,6 @@ __global__ __launch_bounds__(1024) void cgm_rz_kernel(const double* __restrict__
       sc->beta = s / sc->rho_prev;
     }
   }
-}
-
-static bool cgm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// status of a nested C ABI call -> the exception the outer guard reports
-static void cgm_check(int st) {
-  if (st == GG_OK) return;
-  char buf[512];
-  gg_last_error(buf, sizeof buf);
-  throw Error(st, buf);
 }
 
 static int64_t cgm_vec_stride(int64_t n) { return (n + 31) / 32 * 32; }
@@ -289,7 +259,7 @@ namespace gg {
 static void cgm_precond(gg_cgm* c, hipStream_t s, int nb) {
   kron_apply(c->Q, true, c->r, c->u, 0.0, c->mv_work, nullptr, nullptr, s, nullptr, nullptr, 0,
              nullptr);
-  cgm_check(gg_kron_diag_scale((int)c->qm.size(), c->qm.data(), c->lam, c->shift,
+  check_status(gg_kron_diag_scale((int)c->qm.size(), c->qm.data(), c->lam, c->shift,
                                GG_DIAG_DIVIDE, c->u, c->z, s));
   kron_apply(c->Q, false, c->z, c->u, 0.0, c->mv_work, nullptr, nullptr, s, nullptr, nullptr, 0,
              nullptr);
@@ -328,7 +298,7 @@ int gg_cgm_create(const gg_kron* K, double shift, const uint8_t* mask_dev, doubl
     GG_REQUIRE(shift > 0.0, GG_ERR_VALUE,
                "the masked CG needs shift > 0 (W K W alone is singular)");
     int64_t nr = 0, nc = 0, we = 0;
-    gg::cgm_check(gg_kron_shape(K, 0, &nr, &nc, &we));
+    gg::check_status(gg_kron_shape(K, 0, &nr, &nc, &we));
     GG_REQUIRE(nr == nc, GG_ERR_VALUE, "CG needs a square operator");
     GG_REQUIRE((reinterpret_cast<uintptr_t>(work_dev) & 7) == 0, GG_ERR_VALUE,
                "the CG workspace must hold doubles (8-byte aligned)");
@@ -402,7 +372,7 @@ int gg_cgm_start(gg_cgm* c, const double* b_dev, double* x_dev, double rtol, dou
     c->x = x_dev;
     const int64_t n = c->n;
     const int nb = gg::vec_blocks(n);
-    if (gg::cgm_aligned16(b_dev) && gg::cgm_aligned16(x_dev))
+    if (gg::aligned16(b_dev) && gg::aligned16(x_dev))
       hipLaunchKernelGGL(gg::cgm_start_kernel<true>, dim3(nb), dim3(gg::kVecThreads), 0, s,
                          b_dev, c->mask, x_dev, c->r, n, c->partials);
     else
@@ -428,7 +398,7 @@ int gg_cgm_iterate(gg_cgm* c, int max_iters, int check_every, gg_stream stream) 
     const int64_t n = c->n;
     const int nb = gg::vec_blocks(n);
     const bool pre = c->Q != nullptr;
-    const bool x16 = gg::cgm_aligned16(c->x);
+    const bool x16 = gg::aligned16(c->x);
     if (check_every <= 0) check_every = max_iters;
     for (int it = 0; it < max_iters; ++it) {
       hipLaunchKernelGGL(gg::cgm_direction_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, c->p,

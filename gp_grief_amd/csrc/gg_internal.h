@@ -66,6 +66,17 @@ constexpr int kWave = 64;
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the double2 lanes of the vector kernels need 16-byte aligned vectors
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// status of a nested C ABI call -> the exception the outer guard reports
+inline void check_status(int st) {
+  if (st == GG_OK) return;
+  char buf[512];
+  gg_last_error(buf, sizeof buf);
+  throw Error(st, buf);
+}
+
 // ---- device scalar block shared by the Krylov drivers (CG / Lanczos) ----
 constexpr int kXWinMax = 8;       // x_defer mode 3: the largest window
 constexpr int kXWinDefault = 8;   // and the default (GG_CG_XWIN; profiles/r06/b_win)
@@ -229,7 +240,7 @@ inline int vec_blocks(int64_t n) {
 }
 
 // ---- Kronecker eigenvalue diagonal: the factor orders and each factor's
-// offset into the concatenated eigenvalue table (gg_vec.hip, gg_sample.hip)
+// offset into the concatenated eigenvalue table (gg_diag.hip, gg_sample.hip)
 struct KronDiag {
   int d;
   int64_t m[16];
@@ -255,7 +266,7 @@ inline KronDiag make_diag(int d, const int64_t* m, int64_t* n_out) {
 
 #if defined(__HIPCC__)
 // splitmix64's finaliser: the counter-based hash of the Rademacher probes
-// (gg_vec.hip) and of the Gaussian stream (gg_sample.hip)
+// (gg_diag.hip) and of the Gaussian stream (gg_sample.hip)
 __device__ __forceinline__ uint64_t probe_mix(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -283,13 +294,42 @@ __device__ __forceinline__ double block_sum(double v) {
   return s;
 }
 
+// a one-block kernel's sum of `count` block partials; result valid in thread 0
+__device__ __forceinline__ double sum_partials(const double* __restrict__ partials,
+                                               int64_t count) {
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
+  return block_sum(acc);
+}
+
+// the masked kernels' select (gg_cgm.hip, gg_lzm.hip): never a multiply, the
+// masked-out value may be NaN
+__device__ __forceinline__ double sel(uint8_t m, double v) { return m ? v : 0.0; }
+
+// Kernels launched from files other than the one that defines them (no
+// relocatable device code: the others see only these declarations).
 // ---- the unnormalised Lanczos recurrence's one-thread scalar kernels
-// (gg_vec.hip), shared with the masked probe (gg_lzm.hip).
+// (gg_lanczos.hip), shared with the masked probe (gg_lzm.hip).
 // lzs: [0] sV, [1] sP, [2] cy, [3] cu, [4] cp
 __global__ void lz_coef_kernel(double* __restrict__ lzs, const double* __restrict__ dot,
                                double* __restrict__ alpha_out,
                                const double* __restrict__ beta_prev);
 __global__ void lz_beta_kernel(double* __restrict__ lzs, double* __restrict__ beta);
+
+// ---- the single-GPU CG's kernels (gg_vec.hip) that the sharded CG's scalars
+// (gg_cgs.hip) launch too
+__global__ __launch_bounds__(kVecThreads) void cg_xr_update_kernel(
+    double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+    const double* __restrict__ q, int64_t n, const CgScalars* __restrict__ sc,
+    double* __restrict__ partials, int need_pending);
+__global__ __launch_bounds__(1024) void cg_fused_scalars_kernel(
+    const double* __restrict__ rr_part, int64_t nrr, int64_t rr_stride,
+    const double* __restrict__ mv_part, int64_t nmv, int64_t pstride, CgScalars* sc,
+    const double* p_new, int xmode, int rq_ident, int rder);
+__global__ __launch_bounds__(kVecThreads) void cg_x_flush2_kernel(double* __restrict__ x,
+                                                                  int64_t n, int64_t H,
+                                                                  const CgScalars* __restrict__ sc);
+__global__ void cg_x_flushed_kernel(CgScalars* sc);
 #endif
 
 // RAII set of HIP events (timed Lanczos, calibration)
@@ -310,8 +350,8 @@ struct EventSet {
   EventSet& operator=(const EventSet&) = delete;
 };
 
-// ---- the sharded CG's scalar state (gg_vec.hip gg_cgs), for the fused
-// sharded phase 1 in gg_kron.hip ----
+// ---- the sharded CG's scalar state (gg_cgs.hip), for the fused sharded
+// phase 1 in gg_kron.hip ----
 CgScalars* cgs_scalars_ptr(gg_cgs* c);
 double* cgs_rr_part(gg_cgs* c, int64_t cap, int64_t* cap_out);
 void cgs_set_pro_blocks(gg_cgs* c, int64_t nb);
@@ -321,8 +361,12 @@ void launch_dot_partials(const double* x, const double* y, int64_t n, double* pa
                          int nblocks, hipStream_t s);
 void launch_reduce_to(const double* partials, int64_t count, double* out, hipStream_t s);
 // x_defer 2, one half of the active pair (sc->xh; [0, H) or [H, n)) as a
-// streaming kernel sized to sit beside the ring mode products (gg_vec.hip)
+// streaming kernel sized to sit beside the ring mode products
 void launch_x_half(double* x, int64_t n, int64_t H, const CgScalars* sc, hipStream_t s);
+// a gg_cg / gg_cgs handle's scalar block, zeroed (GG_CG_CANCEL_TOL applied)
+void scalars_clear(CgScalars* sc);
+// the Rademacher probe times `scale` on vec_blocks(n) workgroups (gg_diag.hip)
+void launch_probe(uint64_t seed, int probe, double scale, double* z, int64_t n, hipStream_t s);
 
 // ---- environment switches (gg_knobs.hip): the process snapshot of every
 // GG_* variable, taken at the first lookup and re-taken at gg_kron_create /
@@ -330,8 +374,24 @@ void launch_x_half(double* x, int64_t n, int64_t H, const CgScalars* sc, hipStre
 const char* knob(const char* name);
 void knobs_reload();
 
-// ---- the Kronecker operator in its parity-block basis (gg_kronb.hip) ----
 struct BlockOp;
+
+// ---- the Kronecker operator behind the C handle (gg_kron.hip) ----
+// y = (K or K^T) x + shift x; cg / cgp: the fusions of MpFuse (see kron_apply)
+void kron_apply(const gg_kron* K, bool transpose, const double* x, double* y, double shift,
+                double* work, double* dot_partials, const int* skip, hipStream_t stream,
+                int64_t* n_partials_out, const MpFuse* cg, int cgp, hipEvent_t* ev);
+int64_t kron_partials_needed(const gg_kron* K, bool transpose);
+int64_t kron_prologue_blocks(const gg_kron* K);
+int64_t kron_work_elems(const gg_kron* K, bool transpose);
+int64_t kron_n(const gg_kron* K);
+int kron_d(const gg_kron* K);
+void kron_factor_shape(const gg_kron* K, int64_t* rows, int64_t* cols);
+bool kron_first_single_launch(const gg_kron* K);
+int64_t kron_side_half(const gg_kron* K, int64_t n);
+const BlockOp* kron_block(const gg_kron* K);   // nullptr: no block form
+
+// ---- the Kronecker operator in its parity-block basis (gg_kronb.hip) ----
 // nullptr when the operator has no block form (a factor not square, of odd
 // order or not centrosymmetric; d outside 2..6; the last two orders unequal or
 // without a pair kernel; GG_KRON_BLOCK=0 at creation)

@@ -828,8 +828,6 @@ static void plan_sizes(const std::vector<Factor>& fs, int64_t n_in, int64_t& max
   }
 }
 
-int64_t kron_side_half(const gg_kron* K, int64_t n);
-
 void kron_apply(const gg_kron* K, bool transpose, const double* x, double* y, double shift,
                 double* work, double* dot_partials, const int* skip, hipStream_t stream,
                 int64_t* n_partials_out, const MpFuse* cg, int cgp, hipEvent_t* ev) {

@@ -11,7 +11,7 @@
 //   update  w = select(mask, cy Y, 0) + cu u + cp u_prev in place of Y, with
 //           |w|^2 partials            (3 reads + 1 write + the mask, N / 8 of one)
 // and the one-thread scalar kernels of the grid-basis probe (lz_coef_kernel,
-// lz_beta_kernel, gg_vec.hip).  The vectors stay unnormalised with device
+// lz_beta_kernel, gg_lanczos.hip).  The vectors stay unnormalised with device
 // scales as there (v = sV u, v_prev = sP u_prev): no normalisation pass and no
 // masking pass over Y; the start vector is select(mask, z, 0) with sV =
 // 1 / sqrt(n_obs), n_obs counted on the device by the pass that zeroes z.
@@ -23,14 +23,6 @@
 #include "gg_internal.h"
 
 namespace gg {
-
-// defined in gg_kron.hip
-void kron_apply(const gg_kron* K, bool transpose, const double* x, double* y, double shift,
-                double* work, double* dot_partials, const int* skip, hipStream_t stream,
-                int64_t* n_partials_out, const MpFuse* cg, int cgp, hipEvent_t* ev);
-int64_t kron_partials_needed(const gg_kron* K, bool transpose);
-
-__device__ __forceinline__ double lzm_sel(uint8_t m, double v) { return m ? v : 0.0; }
 
 // u = select(mask, u, 0) in place (u holds the +-1 probe); partial observed
 // counts (exact in a double: whole numbers below 2^53)
@@ -46,20 +38,20 @@ __global__ __launch_bounds__(kVecThreads) void lzm_start_kernel(
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
       const uint8_t m0 = mask[2 * i], m1 = mask[2 * i + 1];
       double2 uv = u2[i];
-      uv.x = lzm_sel(m0, uv.x);
-      uv.y = lzm_sel(m1, uv.y);
+      uv.x = sel(m0, uv.x);
+      uv.y = sel(m1, uv.y);
       u2[i] = uv;
       acc += (m0 ? 1.0 : 0.0) + (m1 ? 1.0 : 0.0);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
       const uint8_t m = mask[n - 1];
-      u[n - 1] = lzm_sel(m, u[n - 1]);
+      u[n - 1] = sel(m, u[n - 1]);
       acc += m ? 1.0 : 0.0;
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
       const uint8_t m = mask[i];
-      u[i] = lzm_sel(m, u[i]);
+      u[i] = sel(m, u[i]);
       acc += m ? 1.0 : 0.0;
     }
   }
@@ -93,37 +85,27 @@ __global__ __launch_bounds__(kVecThreads) void lzm_update_kernel(
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
       const double2 a = w2[i], b = v2[i], c = p2[i];
       double2 r;
-      r.x = fma(cp, c.x, fma(cu, b.x, lzm_sel(mask[2 * i], cy * a.x)));
-      r.y = fma(cp, c.y, fma(cu, b.y, lzm_sel(mask[2 * i + 1], cy * a.y)));
+      r.x = fma(cp, c.x, fma(cu, b.x, sel(mask[2 * i], cy * a.x)));
+      r.y = fma(cp, c.y, fma(cu, b.y, sel(mask[2 * i + 1], cy * a.y)));
       w2[i] = r;
       acc = fma(r.x, r.x, acc);
       acc = fma(r.y, r.y, acc);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
       const int64_t i = n - 1;
-      const double r = fma(cp, pv[i], fma(cu, v[i], lzm_sel(mask[i], cy * w[i])));
+      const double r = fma(cp, pv[i], fma(cu, v[i], sel(mask[i], cy * w[i])));
       w[i] = r;
       acc = fma(r, r, acc);
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-      const double r = fma(cp, pv[i], fma(cu, v[i], lzm_sel(mask[i], cy * w[i])));
+      const double r = fma(cp, pv[i], fma(cu, v[i], sel(mask[i], cy * w[i])));
       w[i] = r;
       acc = fma(r, r, acc);
     }
   }
   const double s = block_sum(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-static bool lzm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// status of a nested C ABI call -> the exception the outer guard reports
-static void lzm_check(int st) {
-  if (st == GG_OK) return;
-  char buf[512];
-  gg_last_error(buf, sizeof buf);
-  throw Error(st, buf);
 }
 
 // gg_lanczos_probe_masked / _timed.  step_ms (steps entries, may be null): HIP
@@ -138,7 +120,7 @@ static void lanczos_masked(const gg_kron* K, double shift, const uint8_t* mask, 
   GG_REQUIRE(steps >= 1, GG_ERR_VALUE, "Lanczos needs steps >= 1");
   GG_REQUIRE(shift >= 0.0, GG_ERR_VALUE, "Lanczos needs shift >= 0");
   int64_t nr = 0, nc = 0, we = 0;
-  lzm_check(gg_kron_shape(K, 0, &nr, &nc, &we));
+  check_status(gg_kron_shape(K, 0, &nr, &nc, &we));
   GG_REQUIRE(nr == nc, GG_ERR_VALUE, "Lanczos needs a square operator");
   GG_REQUIRE(we <= nr, GG_ERR_VALUE, "non-square factors are not supported here");
   hipStream_t s = as_stream(stream);
@@ -162,8 +144,8 @@ static void lanczos_masked(const gg_kron* K, double shift, const uint8_t* mask, 
   GG_HIP(hipMemsetAsync(zero, 0, sizeof(double), s));
   GG_HIP(hipMemsetAsync(P, 0, n * sizeof(double), s));
   // u_0 = select(mask, z, 0), z the +-1 probe over all n grid points
-  lzm_check(gg_probe_fill(seed, probe, V, n, stream));
-  if (lzm_aligned16(V))
+  check_status(gg_probe_fill(seed, probe, V, n, stream));
+  if (aligned16(V))
     hipLaunchKernelGGL(lzm_start_kernel<true>, dim3(nb), dim3(kVecThreads), 0, s, V, mask, n,
                        parts);
   else
@@ -185,7 +167,7 @@ static void lanczos_masked(const gg_kron* K, double shift, const uint8_t* mask, 
     hipLaunchKernelGGL(lz_coef_kernel, dim3(1), dim3(1), 0, s, lzs, dot, alphas + j, beta_prev);
     GG_LAUNCH_CHECK();
     // 16-byte lanes when all three vectors are 16-byte aligned
-    if (lzm_aligned16(W) && lzm_aligned16(V) && lzm_aligned16(P))
+    if (aligned16(W) && aligned16(V) && aligned16(P))
       hipLaunchKernelGGL(lzm_update_kernel<true>, dim3(nb), dim3(kVecThreads), 0, s, W, V, P,
                          mask, n, lzs, parts);
     else

@@ -248,8 +248,6 @@ __global__ __launch_bounds__(kVecThreads) void sample_accumulate_kernel(
   }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // blocks of a grid-stride kernel over the (n + 1) / 2 pairs of n elements
 static int pair_blocks(int64_t n) { return vec_blocks(n + 1); }
 

@@ -3,32 +3,19 @@
 // one deterministic single-block reduction).  No float atomics anywhere, so
 // every dot product is bitwise reproducible run to run.
 //
+// Here: dot / reduce / axpby and the single-GPU CG (Lanczos: gg_lanczos.hip;
+// diagonal kernels: gg_diag.hip; the sharded CG's scalars: gg_cgs.hip).
+//
 // The reference has no CG or Lanczos; the CG recurrence is the
 // one of scipy.sparse.linalg.cg (oracle/cg.py restates it), driven here with
 // every scalar resident on the device so the host only polls convergence.
 #include <cmath>
-#include <vector>
-
 #include <map>
+#include <vector>
 
 #include "gg_internal.h"
 
 namespace gg {
-
-// defined in gg_kron.hip
-void kron_apply(const gg_kron* K, bool transpose, const double* x, double* y, double shift,
-                double* work, double* dot_partials, const int* skip, hipStream_t stream,
-                int64_t* n_partials_out, const MpFuse* cg, int cgp, hipEvent_t* ev);
-int64_t kron_partials_needed(const gg_kron* K, bool transpose);
-int64_t kron_prologue_blocks(const gg_kron* K);
-int64_t kron_work_elems(const gg_kron* K, bool transpose);
-int64_t kron_n(const gg_kron* K);
-int kron_d(const gg_kron* K);
-bool kron_first_single_launch(const gg_kron* K);
-int64_t kron_side_half(const gg_kron* K, int64_t n);
-const BlockOp* kron_block(const gg_kron* K);
-
-// wave_sum / block_sum / vec_blocks: gg_internal.h (shared with gg_cgm.hip)
 
 __global__ __launch_bounds__(kVecThreads) void dot_partials_kernel(const double* __restrict__ x,
                                                                    const double* __restrict__ y,
@@ -64,13 +51,9 @@ __global__ __launch_bounds__(kVecThreads) void dot_partials_unaligned_kernel(
 
 __global__ __launch_bounds__(1024) void reduce_kernel(const double* __restrict__ partials,
                                                       int64_t count, double* __restrict__ out) {
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) *out = s;
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 void launch_dot_partials(const double* x, const double* y, int64_t n, double* partials,
                          int nblocks, hipStream_t s) {
@@ -101,9 +84,7 @@ __global__ __launch_bounds__(kVecThreads) void axpby_kernel(double a, const doub
 __global__ __launch_bounds__(1024) void cg_alpha_kernel(const double* __restrict__ partials,
                                                         int64_t count, CgScalars* sc) {
   if (sc->done) return;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     sc->pq = s;
     sc->alpha = sc->rho / s;
@@ -168,9 +149,7 @@ __global__ __launch_bounds__(1024) void cg_rho_kernel(const double* __restrict__
                                                       int need_pending) {
   if (sc->done || (need_pending && !sc->pending)) return;
   if (need_pending == 2 && !sc->repair) return;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     sc->rho_prev = sc->rho;
     sc->rho = s;
@@ -576,9 +555,7 @@ __global__ void cg_close_rho_kernel(CgScalars* sc, const double* rr) {
 
 __global__ void cg_init_kernel(const double* __restrict__ partials, int64_t count,
                                CgScalars* sc, double rtol, double atol) {
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += partials[i];
-  const double s = block_sum(acc);
+  const double s = sum_partials(partials, count);
   if (threadIdx.x == 0) {
     sc->rho = s;
     sc->rho_prev = 0.0;
@@ -604,326 +581,10 @@ __global__ void cg_init_kernel(const double* __restrict__ partials, int64_t coun
   }
 }
 
-// ----------------------------------------------------------- Lanczos kernels
-// ---- fused Lanczos (gg_lanczos_probe).  The Lanczos vectors are kept
-// unnormalised: V holds u with v = sV u, P holds u_prev with v_prev = sP u_prev
-// (lzs[0], lzs[1]).  The matvec Y = K u + shift u has alpha's dot u.Y in its
-// last epilogue (v.Av = sV^2 u.Y), and ONE streaming pass forms
-// w = Av - alpha v - beta v_prev = cy Y + cu u + cp u_prev with |w|^2, in
-// place of Y: 13 passes over N per step instead of 18 (no normalisation pass;
-// the next step's v is w with sV = 1 / beta).  With an even number of
-// factors that pass is the next matvec's prologue instead (CGP 3 in
-// gg_kron.hip: w is the MFMA operand, written over u_prev).  alpha = v.Av: the oracle's
-// v.(Av - beta v_prev) differs by beta v.v_prev, rounding-level while the
-// three-term recurrence keeps local orthogonality.
-// lzs: [0] sV, [1] sP, [2] cy, [3] cu, [4] cp
-__global__ void lz_coef_kernel(double* __restrict__ lzs, const double* __restrict__ dot,
-                               double* __restrict__ alpha_out,
-                               const double* __restrict__ beta_prev) {
-  const double sV = lzs[0], sP = lzs[1];
-  const double a = sV * sV * *dot;
-  *alpha_out = a;
-  lzs[2] = sV;
-  lzs[3] = -a * sV;
-  lzs[4] = -(*beta_prev) * sP;
-}
-
-// w = cy w + cu v + cp p (in place), partial w.w; 16-byte lanes when all
-// three vectors are 16-byte aligned (wide), else 8-byte
-__global__ __launch_bounds__(kVecThreads) void lz_update_kernel(
-    double* __restrict__ w, const double* __restrict__ v, const double* __restrict__ pv,
-    int64_t n, const double* __restrict__ lzs, double* __restrict__ partials, int wide) {
-  const double cy = lzs[2], cu = lzs[3], cp = lzs[4];
-  double acc = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (!wide) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-      const double r = fma(cp, pv[i], fma(cu, v[i], cy * w[i]));
-      w[i] = r;
-      acc = fma(r, r, acc);
-    }
-    const double s = block_sum(acc);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
-    return;
-  }
-  const int64_t n2 = n / 2;
-  double2* __restrict__ w2 = reinterpret_cast<double2*>(w);
-  const double2* __restrict__ v2 = reinterpret_cast<const double2*>(v);
-  const double2* __restrict__ p2 = reinterpret_cast<const double2*>(pv);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
-    const double2 a = w2[i], b = v2[i], c = p2[i];
-    double2 r;
-    r.x = fma(cp, c.x, fma(cu, b.x, cy * a.x));
-    r.y = fma(cp, c.y, fma(cu, b.y, cy * a.y));
-    w2[i] = r;
-    acc = fma(r.x, r.x, acc);
-    acc = fma(r.y, r.y, acc);
-  }
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t i = n - 1;
-    const double r = fma(cp, pv[i], fma(cu, v[i], cy * w[i]));
-    w[i] = r;
-    acc = fma(r, r, acc);
-  }
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// beta = sqrt(|w|^2) ; next step: v_prev = v (sP = sV), v = w (sV = 1 / beta)
-__global__ void lz_beta_kernel(double* __restrict__ lzs, double* __restrict__ beta) {
-  const double b = sqrt(*beta);
-  *beta = b;
-  lzs[1] = lzs[0];
-  lzs[0] = b > 0.0 ? 1.0 / b : 0.0;
-}
-
-// The block-basis Lanczos step's scalars (lanczos_block), after step j's
-// three launches: rr = |w_{j-1}|^2 (the prologue's partials; |u_0|^2 = 1 at
-// j = 0), dot = u_j.Y_j (the pair launch's p.q partials).  beta_{j-1} =
-// sqrt(rr), v_j = u_j / beta_{j-1} (sV), v_{j-1} = sP u_{j-1} (the previous
-// sV), alpha_j = sV^2 dot, and the next prologue's w_j = A v_j - alpha_j v_j -
-// beta_{j-1} v_{j-1} = cy Y_j + cu u_j + cp u_{j-1}.
-// lzs: [0] sV, [1] sP, [2] cy, [3] cu, [4] cp
-__global__ __launch_bounds__(1024) void lzb_step_kernel(const double* __restrict__ rr_part,
-                                                        int64_t nrr,
-                                                        const double* __restrict__ dot_part,
-                                                        int64_t ndot, double* __restrict__ lzs,
-                                                        double* __restrict__ alpha_out,
-                                                        double* __restrict__ beta_out,
-                                                        int first) {
-  double a0 = 0.0, a1 = 0.0;
-  for (int64_t i = threadIdx.x; i < nrr; i += blockDim.x) a0 += rr_part[i];
-  for (int64_t i = threadIdx.x; i < ndot; i += blockDim.x) a1 += dot_part[i];
-  const double rr = block_sum(a0);
-  __syncthreads();
-  const double dot = block_sum(a1);
-  if (threadIdx.x == 0) {
-    const double beta = sqrt(rr);
-    if (!first) *beta_out = beta;
-    const double sP = lzs[0];
-    const double sV = beta > 0.0 ? 1.0 / beta : 0.0;
-    const double alpha = sV * sV * dot;
-    *alpha_out = alpha;
-    lzs[0] = sV;
-    lzs[1] = sP;
-    lzs[2] = sV;
-    lzs[3] = -alpha * sV;
-    lzs[4] = first ? 0.0 : -beta * sP;
-  }
-}
-
-// A[i][j] *= w[i] (mode 0) or /= w[i] (mode 1); square (mode 2): A = A * A
-__global__ __launch_bounds__(kVecThreads) void scale_rows_kernel(double* __restrict__ A,
-                                                                 int64_t rows, int64_t cols,
-                                                                 const double* __restrict__ w,
-                                                                 int mode) {
-  const int64_t total = rows * cols;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-    const double a = A[e];
-    if (mode == 2) {
-      A[e] = a * a;
-    } else {
-      const double s = w[e / cols];
-      A[e] = mode == 0 ? a * s : a / s;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kVecThreads) void diag_divide_kernel(const double* __restrict__ t,
-                                                                  double shift,
-                                                                  const double* __restrict__ x,
-                                                                  double* __restrict__ y,
-                                                                  int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    y[i] = x[i] / (t[i] + shift);
-}
-
-// Rademacher probe, bit-identical to oracle/cg.py probe_signs (splitmix64;
-// probe_mix: gg_internal.h)
-__global__ __launch_bounds__(kVecThreads) void probe_kernel(uint64_t base, double scale,
-                                                            double* __restrict__ z, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint64_t h = probe_mix(base + (uint64_t)i * 0x9E3779B97F4A7C15ull);
-    z[i] = (h >> 63) == 0 ? scale : -scale;
-  }
-}
-
-static uint64_t probe_base(uint64_t seed, int probe) {
-  return (((seed & 0xffffffffull) << 32) ^ (((uint64_t)probe & 0xffffull) << 16) ^
-          0x9E3779B97F4A7C15ull);
-}
-
-// ----------------------------------------------- Kronecker eigenvalue diagonal
-// (KronDiag, make_diag: gg_internal.h, shared with gg_sample.hip)
-__device__ __forceinline__ double kron_eig_at(const KronDiag& kd, const double* lam, int64_t i) {
-  double t = 1.0;
-  for (int k = kd.d - 1; k >= 0; --k) {
-    const int64_t ik = i % kd.m[k];
-    i /= kd.m[k];
-    t *= lam[kd.off[k] + ik];
-  }
-  return t;
-}
-
-__global__ __launch_bounds__(kVecThreads) void diag_scale_kernel(KronDiag kd,
-                                                                 const double* __restrict__ lam,
-                                                                 double shift, int mode,
-                                                                 const double* __restrict__ x,
-                                                                 double* __restrict__ y,
-                                                                 int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double t = kron_eig_at(kd, lam, i);
-    double v;
-    if (mode == GG_DIAG_DIVIDE)
-      v = x[i] / (t + shift);
-    else if (mode == GG_DIAG_POSTVAR)
-      v = t * shift / (t + shift);
-    else
-      v = x[i] * (t + shift);
-    y[i] = v;
-  }
-}
-
-__global__ __launch_bounds__(kVecThreads) void logdet_kernel(KronDiag kd,
-                                                             const double* __restrict__ lam,
-                                                             double shift, int64_t n,
-                                                             double* __restrict__ partials) {
-  // the last factor varies fastest: decode the head once per run of m_last
-  const int64_t ml = kd.m[kd.d - 1];
-  const int64_t nhead = n / ml;
-  const double* lastl = lam + kd.off[kd.d - 1];
-  double acc = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int64_t h = i / ml;
-    const int64_t l = i - h * ml;
-    double t = lastl[l];
-    int64_t hh = h;
-    for (int k = kd.d - 2; k >= 0; --k) {
-      const int64_t ik = hh % kd.m[k];
-      hh /= kd.m[k];
-      t *= lam[kd.off[k] + ik];
-    }
-    acc += log(t + shift);
-  }
-  (void)nhead;
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// ---------------------------------------------- trace pass of the LML gradient
-// out[p] = sum_g prod_f num[p][off_f + g_f] / (prod_f lam[off_f + g_f] + shift).
-// A work item is (head index, segment of the last factor): the head -- every
-// factor but the last -- is decoded once per item, its eigenvalue product and
-// the kPC head numerators of this block's row chunk (blockIdx.y) stay in
-// registers, and the run over the segment is one FMA and one reciprocal per
-// grid point, shared by the kPC accumulators (a multiply and an FMA each).
-// No memory stream: the operands are the (P + 1) sum_f m_f table entries.
-// kIdx is uint32_t wherever N < 2^31 (the decode's divisions are the cost of
-// an item), int64_t beyond.  partials: P rows of gridDim.x.
-constexpr int kTraceRows = 8;    // rows of num per block (register accumulators)
-constexpr int kTraceSeg = 16;    // shortest segment worth a head decode
-constexpr int kTraceSegMax = 128;
-constexpr int64_t kTraceItems = 131072;  // items that fill the device
-
-template <int kPC, typename kIdx>
-__global__ __launch_bounds__(kVecThreads) void trace_ratio_kernel(
-    KronDiag kd, const double* __restrict__ lam, double shift, int P, int64_t rowlen,
-    const double* __restrict__ num, kIdx items, kIdx nseg, int seg,
-    double* __restrict__ partials) {
-  const int d = kd.d;
-  const int row0 = blockIdx.y * kPC;
-  const kIdx ml = (kIdx)kd.m[d - 1];
-  const int64_t offl = kd.off[d - 1];
-  // rows past P (the last chunk's tail) read row P - 1 and are never stored
-  const double* nrow[kPC];
-#pragma unroll
-  for (int q = 0; q < kPC; ++q) nrow[q] = num + (int64_t)min(row0 + q, P - 1) * rowlen;
-  double acc[kPC];
-#pragma unroll
-  for (int q = 0; q < kPC; ++q) acc[q] = 0.0;
-  const kIdx stride = (kIdx)gridDim.x * blockDim.x;
-  for (kIdx it = (kIdx)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    kIdx hh = it / nseg;
-    const kIdx sg = it - hh * nseg;
-    double hl = 1.0;
-    double hn[kPC];
-#pragma unroll
-    for (int q = 0; q < kPC; ++q) hn[q] = 1.0;
-    for (int k = d - 2; k >= 0; --k) {
-      const kIdx mk = (kIdx)kd.m[k];
-      const kIdx nx = hh / mk;
-      const int64_t o = kd.off[k] + (int64_t)(hh - nx * mk);
-      hh = nx;
-      hl *= lam[o];
-#pragma unroll
-      for (int q = 0; q < kPC; ++q) hn[q] *= nrow[q][o];
-    }
-    const kIdx l0 = sg * (kIdx)seg;
-    const kIdx l1 = min(l0 + (kIdx)seg, ml);
-    for (kIdx l = l0; l < l1; ++l) {
-      const int64_t o = offl + (int64_t)l;
-      const double r = 1.0 / fma(hl, lam[o], shift);
-#pragma unroll
-      for (int q = 0; q < kPC; ++q) acc[q] = fma(hn[q] * nrow[q][o], r, acc[q]);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < kPC; ++q) {
-    const double s = block_sum(acc[q]);
-    __syncthreads();
-    if (threadIdx.x == 0 && row0 + q < P)
-      partials[(int64_t)(row0 + q) * gridDim.x + blockIdx.x] = s;
-  }
-}
-
-// out[blockIdx.x] = sum of row blockIdx.x of partials (rows of `count`)
-__global__ __launch_bounds__(1024) void reduce_rows_kernel(const double* __restrict__ partials,
-                                                           int64_t count,
-                                                           double* __restrict__ out) {
-  const double* row = partials + (int64_t)blockIdx.x * count;
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += blockDim.x) acc += row[i];
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-
-template <typename kIdx>
-static void launch_trace_ratio(int pc, dim3 grid, hipStream_t s, const KronDiag& kd,
-                               const double* lam, double shift, int P, int64_t rowlen,
-                               const double* num, int64_t items, int64_t nseg, int seg,
-                               double* partials) {
-#define GG_TRACE_CASE(PC)                                                                  \
-  case PC:                                                                                 \
-    hipLaunchKernelGGL((trace_ratio_kernel<PC, kIdx>), grid, dim3(kVecThreads), 0, s, kd,  \
-                       lam, shift, P, rowlen, num, (kIdx)items, (kIdx)nseg, seg, partials); \
-    break;
-  switch (pc) {
-    GG_TRACE_CASE(1)
-    GG_TRACE_CASE(2)
-    GG_TRACE_CASE(3)
-    GG_TRACE_CASE(4)
-    GG_TRACE_CASE(5)
-    GG_TRACE_CASE(6)
-    GG_TRACE_CASE(7)
-    default:
-      GG_TRACE_CASE(8)
-  }
-#undef GG_TRACE_CASE
-  GG_LAUNCH_CHECK();
-}
-
-}  // namespace gg
-
 // ------------------------------------------------------------------- CG state
-namespace gg {
 // a handle's scalar block: zeroed, with the cancellation threshold of the
 // knob snapshot (GG_CG_CANCEL_TOL, tests: forces the repair / restart paths)
-static void scalars_clear(CgScalars* sc) {
+void scalars_clear(CgScalars* sc) {
   GG_HIP(hipMemset(sc, 0, sizeof(CgScalars)));
   const char* e = knob("GG_CG_CANCEL_TOL");
   if (e) {
@@ -1091,122 +752,6 @@ int gg_axpby(double a, const double* x_dev, double b, double* y_dev, int64_t n,
     if (n == 0) return;
     hipLaunchKernelGGL(gg::axpby_kernel, dim3(gg::vec_blocks(2 * n)), dim3(gg::kVecThreads),
                        0, gg::as_stream(stream), a, x_dev, b, y_dev, n);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_diag_divide(const double* t_dev, double shift, const double* x_dev, double* y_dev,
-                   int64_t n, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(t_dev && x_dev && y_dev && n >= 0, GG_ERR_VALUE, "bad argument");
-    if (n == 0) return;
-    hipLaunchKernelGGL(gg::diag_divide_kernel, dim3(gg::vec_blocks(2 * n)),
-                       dim3(gg::kVecThreads), 0, gg::as_stream(stream), t_dev, shift, x_dev,
-                       y_dev, n);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_scale_rows(double* A_dev, int64_t rows, int64_t cols, const double* w_dev, int mode,
-                  gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(A_dev && rows >= 0 && cols >= 0 && mode >= 0 && mode <= 2, GG_ERR_VALUE,
-               "bad argument");
-    GG_REQUIRE(mode == 2 || w_dev, GG_ERR_VALUE, "w required");
-    if (rows * cols == 0) return;
-    hipLaunchKernelGGL(gg::scale_rows_kernel, dim3(gg::vec_blocks(2 * rows * cols)),
-                       dim3(gg::kVecThreads), 0, gg::as_stream(stream), A_dev, rows, cols, w_dev,
-                       mode);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_kron_diag_scale(int d, const int64_t* m, const double* lam_dev, double shift, int mode,
-                       const double* x_dev, double* y_dev, gg_stream stream) {
-  return gg::guard([&] {
-    int64_t n = 0;
-    gg::KronDiag kd = gg::make_diag(d, m, &n);
-    GG_REQUIRE(lam_dev && y_dev, GG_ERR_VALUE, "NULL argument");
-    GG_REQUIRE(mode == GG_DIAG_POSTVAR || x_dev, GG_ERR_VALUE, "x required");
-    GG_REQUIRE(mode >= 0 && mode <= 2, GG_ERR_VALUE, "bad mode");
-    hipLaunchKernelGGL(gg::diag_scale_kernel, dim3(gg::vec_blocks(2 * n)),
-                       dim3(gg::kVecThreads), 0, gg::as_stream(stream), kd, lam_dev, shift,
-                       mode, x_dev, y_dev, n);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_kron_logdet_shifted(int d, const int64_t* m, const double* lam_dev, double shift,
-                           double* out_host, gg_stream stream) {
-  return gg::guard([&] {
-    int64_t n = 0;
-    gg::KronDiag kd = gg::make_diag(d, m, &n);
-    GG_REQUIRE(lam_dev && out_host, GG_ERR_VALUE, "NULL argument");
-    hipStream_t s = gg::as_stream(stream);
-    double* buf = nullptr;
-    GG_HIP(hipMallocAsync(&buf, (gg::kVecBlocks + 1) * sizeof(double), s));
-    const int nb = gg::vec_blocks(2 * n);
-    hipLaunchKernelGGL(gg::logdet_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, kd, lam_dev,
-                       shift, n, buf);
-    GG_LAUNCH_CHECK();
-    gg::launch_reduce_to(buf, nb, buf + gg::kVecBlocks, s);
-    GG_HIP(hipMemcpyAsync(out_host, buf + gg::kVecBlocks, sizeof(double),
-                          hipMemcpyDeviceToHost, s));
-    GG_HIP(hipFreeAsync(buf, s));
-    GG_HIP(hipStreamSynchronize(s));
-  });
-}
-
-int gg_kron_trace_ratio(int d, const int64_t* m, const double* lam_dev, double shift, int P,
-                        const double* num_dev, double* out_host, gg_stream stream) {
-  return gg::guard([&] {
-    int64_t n = 0;
-    gg::KronDiag kd = gg::make_diag(d, m, &n);
-    GG_REQUIRE(P >= 0, GG_ERR_VALUE, "P must be >= 0");
-    GG_REQUIRE(lam_dev && num_dev && out_host, GG_ERR_VALUE, "NULL argument");
-    if (P == 0) return;
-    hipStream_t s = gg::as_stream(stream);
-    // items: (head, segment of the last factor).  Whole runs where the heads
-    // alone fill the device; shorter segments (never under kTraceSeg points,
-    // the decode's worth) on a grid with few heads, capped so that one
-    // thread's chain of additions stays short.
-    const int64_t ml = kd.m[d - 1], nhead = n / ml;
-    const int64_t want = gg::ceil_div(gg::kTraceItems, nhead);
-    int64_t seg = std::max(gg::ceil_div(ml, want), std::min<int64_t>(ml, gg::kTraceSeg));
-    seg = std::min<int64_t>(seg, gg::kTraceSegMax);
-    const int64_t nseg = gg::ceil_div(ml, seg), items = nhead * nseg;
-    const int nb = (int)std::min<int64_t>(gg::kVecBlocks, gg::ceil_div(items, gg::kVecThreads));
-    // P rows in equal chunks of at most kTraceRows, one chunk per blockIdx.y
-    const int nchunk = (P + gg::kTraceRows - 1) / gg::kTraceRows;
-    const int pc = (P + nchunk - 1) / nchunk;
-    GG_REQUIRE(nchunk <= 65535, GG_ERR_VALUE, "too many numerator rows");
-    int64_t rowlen = 0;
-    for (int k = 0; k < d; ++k) rowlen += kd.m[k];
-    double* buf = nullptr;
-    GG_HIP(hipMallocAsync(&buf, ((int64_t)P * nb + P) * sizeof(double), s));
-    double* out_dev = buf + (int64_t)P * nb;
-    const dim3 grid(nb, nchunk);
-    if (n < (int64_t(1) << 31))
-      gg::launch_trace_ratio<uint32_t>(pc, grid, s, kd, lam_dev, shift, P, rowlen, num_dev, items,
-                                       nseg, (int)seg, buf);
-    else
-      gg::launch_trace_ratio<int64_t>(pc, grid, s, kd, lam_dev, shift, P, rowlen, num_dev, items,
-                                      nseg, (int)seg, buf);
-    hipLaunchKernelGGL(gg::reduce_rows_kernel, dim3(P), dim3(1024), 0, s, buf, (int64_t)nb,
-                       out_dev);
-    GG_LAUNCH_CHECK();
-    GG_HIP(hipMemcpyAsync(out_host, out_dev, P * sizeof(double), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipFreeAsync(buf, s));
-    GG_HIP(hipStreamSynchronize(s));
-  });
-}
-
-int gg_probe_fill(uint64_t seed, int probe, double* z_dev, int64_t n, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(z_dev && n >= 0, GG_ERR_VALUE, "bad argument");
-    if (n == 0) return;
-    hipLaunchKernelGGL(gg::probe_kernel, dim3(gg::vec_blocks(2 * n)), dim3(gg::kVecThreads),
-                       0, gg::as_stream(stream), gg::probe_base(seed, probe), 1.0, z_dev, n);
     GG_LAUNCH_CHECK();
   });
 }
@@ -2081,733 +1626,6 @@ int gg_cg_status(gg_cg* cg, int* iters, int* converged, double* resid_norm, doub
     if (converged) *converged = (h.done && std::sqrt(h.rho) < h.tol) || h.bnorm == 0.0;
     if (resid_norm) *resid_norm = std::sqrt(h.rho);
     if (tol) *tol = h.tol;
-  });
-}
-
-}  // extern "C"
-
-namespace gg {
-
-
-// gg_lanczos_probe / gg_lanczos_probe_timed.  step_ms (steps entries, may be
-// null): HIP events on the stream at every step boundary -- the first after
-// the probe is drawn, so allocation, the u_prev memset and the probe kernel
-// are outside -- and the last after the final |w|^2 reduction, before the
-// alphas / betas are copied back; launch_ms (d entries, may be null): the
-// summed time of each mode-product position over the steps.
-static void lanczos_probe(const gg_kron* K, double shift, uint64_t seed, int probe, int steps,
-                          double* work_dev, double* alphas_host, double* betas_host,
-                          int* steps_done, double* step_ms, double* launch_ms,
-                          gg_stream stream);
-static bool lanczos_use_block(const gg_kron* K);
-
-}  // namespace gg
-
-extern "C" {
-
-int gg_lanczos_probe(const gg_kron* K, double shift, uint64_t seed, int probe, int steps,
-                     double* work_dev, double* alphas_host, double* betas_host,
-                     int* steps_done, gg_stream stream) {
-  return gg::guard([&] {
-    gg::lanczos_probe(K, shift, seed, probe, steps, work_dev, alphas_host, betas_host,
-                      steps_done, nullptr, nullptr, stream);
-  });
-}
-
-int gg_lanczos_info(const gg_kron* K, int* block, int* launches) {
-  return gg::guard([&] {
-    GG_REQUIRE(K && block && launches, GG_ERR_VALUE, "NULL argument");
-    const bool b = gg::lanczos_use_block(K);
-    *block = b ? 1 : 0;
-    *launches = b ? gg::block_launches(gg::kron_block(K)) : gg::kron_d(K);
-  });
-}
-
-int gg_lanczos_probe_timed(const gg_kron* K, double shift, uint64_t seed, int probe, int steps,
-                           double* work_dev, double* alphas_host, double* betas_host,
-                           int* steps_done, double* step_ms_host, double* launch_ms_host,
-                           gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(step_ms_host != nullptr, GG_ERR_VALUE, "step_ms_host is NULL");
-    gg::lanczos_probe(K, shift, seed, probe, steps, work_dev, alphas_host, betas_host,
-                      steps_done, step_ms_host, launch_ms_host, stream);
-  });
-}
-
-}  // extern "C"
-
-namespace gg {
-
-// the block basis for the probe where the operator has one with d >= 3 (the
-// Lanczos tridiagonal is invariant under the orthogonal fold P: the probe z
-// becomes P z, the operator P K P^T); GG_LZ_BASIS=0 (snapshot) keeps the grid
-static bool lanczos_use_block(const gg_kron* K) {
-  const BlockOp* B = kron_block(K);
-  // unpadded layouts only: the probe's workspace is 4 n (the grid's n)
-  if (B == nullptr || block_d(B) < 3 || block_n(B) != kron_n(K)) return false;
-  const char* e = knob("GG_LZ_BASIS");
-  if (e) return atoi(e) != 0;
-  return block_efficient(B);
-}
-
-// The fused Lanczos step in the parity-block basis: d - 1 launches and 10
-// passes over N per step -- the first launch's prologue forms w_{j-1} = cy Y +
-// cu u + cp u_prev (KIND 4: read Y, u, u_prev, write w over u_prev and the
-// launch's output over Y), the plain launches 2 each, the pair launch reads
-// its slab and w and writes Y_j = (K + shift) w with the u.Y partials.  One
-// fold of the probe before, no unfold (only the tridiagonal leaves).
-static void lanczos_block(const gg_kron* K, double shift, uint64_t seed, int probe, int steps,
-                          double* work_dev, double* alphas_host, double* betas_host,
-                          int* steps_done, double* step_ms, double* launch_ms,
-                          gg_stream stream) {
-  hipStream_t s = gg::as_stream(stream);
-  const BlockOp* B = kron_block(K);
-  const int64_t n = block_n(B);
-  const int L = block_launches(B);
-  double* P = work_dev;          // u_prev; w is written over it
-  double* V = work_dev + n;      // u (v = sV u)
-  double* W = work_dev + 2 * n;  // Y of the previous step (the chain runs in place on it)
-  double* W2 = work_dev + 3 * n; // the pair launch's output
-  const int nb = vec_blocks(n);
-  const int64_t npart = std::max<int64_t>(block_partials_needed(B), kVecBlocks);
-  const int64_t nrr = std::max<int64_t>(block_prologue_blocks(B), 1);
-  // [alphas | betas | partials (3 x npart: p.q, r.q, q.q) | |w|^2 partials | lzs(8)]
-  double* scal = nullptr;
-  GG_HIP(hipMallocAsync(&scal, (2 * (size_t)steps + 3 * npart + nrr + 8) * sizeof(double), s));
-  double* alphas = scal;
-  double* betas = scal + steps;
-  double* parts = scal + 2 * steps;
-  double* rrparts = parts + 3 * npart;
-  double* lzs = rrparts + nrr;
-  // step 0's prologue copies u_0: w = 0 Y + 1 u + 0 u_prev (Y, u_prev zeroed)
-  const double init[5] = {1.0, 0.0, 0.0, 1.0, 0.0};
-  GG_HIP(hipMemcpyAsync(lzs, init, sizeof(init), hipMemcpyHostToDevice, s));
-  GG_HIP(hipMemsetAsync(P, 0, n * sizeof(double), s));
-  GG_HIP(hipMemsetAsync(W, 0, n * sizeof(double), s));
-  // the probe (grid layout, |z| = 1) into W2, folded into V
-  hipLaunchKernelGGL(probe_kernel, dim3(nb), dim3(kVecThreads), 0, s, probe_base(seed, probe),
-                     1.0 / std::sqrt((double)n), W2, n);
-  GG_LAUNCH_CHECK();
-  block_fold(B, false, W2, V, nullptr, s);
-  const bool timed = step_ms != nullptr;
-  // step boundaries, then the closing pass's end (ev[steps] -> ev[steps + 1])
-  EventSet sev(timed ? (size_t)steps + 2 : 0);
-  EventSet mev(timed && launch_ms ? (size_t)steps * (L + 1) : 0);
-  auto mp_ev = [&](int j) -> hipEvent_t* {
-    return mev.ev.empty() ? nullptr : mev.ev.data() + (size_t)j * (L + 1);
-  };
-  if (timed) GG_HIP(hipEventRecord(sev.ev[0], s));
-  for (int j = 0; j < steps; ++j) {
-    MpFuse lf;
-    lf.r = V;
-    lf.q_old = W;
-    lf.p_out = P;
-    lf.coef = lzs + 2;
-    lf.rr_part = rrparts;
-    lf.rr_cap = nrr;
-    int64_t pro_blocks = 0;
-    lf.pro_blocks = &pro_blocks;
-    lf.blk_q_out = W2;
-    lf.pstride = npart;
-    int64_t np = 0;
-    block_apply(B, P, W, shift, nullptr, parts, nullptr, s, &np, &lf, 3, mp_ev(j));
-    GG_REQUIRE(pro_blocks > 0 && pro_blocks <= nrr, GG_ERR_RUNTIME,
-               "Lanczos: no prologue launch recorded");
-    hipLaunchKernelGGL(lzb_step_kernel, dim3(1), dim3(1024), 0, s, rrparts, pro_blocks, parts, np,
-                       lzs, alphas + j, j > 0 ? betas + (j - 1) : betas, j == 0 ? 1 : 0);
-    GG_LAUNCH_CHECK();
-    std::swap(P, V);    // u_prev <- u_j's predecessor ... u <- w (= u_j)
-    std::swap(W, W2);   // Y_j becomes the next step's chain
-    if (timed && j + 1 < steps) GG_HIP(hipEventRecord(sev.ev[j + 1], s));
-  }
-  // the closing pass, once per probe: beta_{steps-1} = |w_{steps-1}| (one
-  // streaming pass, in place of Y; T_k itself needs beta_0 .. beta_{k-2})
-  if (timed) GG_HIP(hipEventRecord(sev.ev[steps], s));
-  const int wide = ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(V) |
-                     reinterpret_cast<uintptr_t>(P)) & 15) == 0;
-  hipLaunchKernelGGL(lz_update_kernel, dim3(nb), dim3(kVecThreads), 0, s, W, V, P, n, lzs + 0,
-                     parts, wide);
-  GG_LAUNCH_CHECK();
-  launch_reduce_to(parts, nb, betas + (steps - 1), s);
-  hipLaunchKernelGGL(lz_beta_kernel, dim3(1), dim3(1), 0, s, lzs, betas + (steps - 1));
-  GG_LAUNCH_CHECK();
-  if (timed) GG_HIP(hipEventRecord(sev.ev[steps + 1], s));
-  GG_HIP(hipMemcpyAsync(alphas_host, alphas, steps * sizeof(double), hipMemcpyDeviceToHost, s));
-  GG_HIP(hipMemcpyAsync(betas_host, betas, steps * sizeof(double), hipMemcpyDeviceToHost, s));
-  GG_HIP(hipFreeAsync(scal, s));
-  GG_HIP(hipStreamSynchronize(s));
-  if (timed) {
-    for (int j = 0; j < steps; ++j) {
-      float ms = 0.f;
-      GG_HIP(hipEventElapsedTime(&ms, sev.ev[j], sev.ev[j + 1]));
-      step_ms[j] = ms;
-    }
-    if (launch_ms) {
-      const int d = kron_d(K);
-      for (int k = 0; k < d; ++k) launch_ms[k] = 0.0;
-      for (int j = 0; j < steps; ++j)
-        for (int k = 0; k < L; ++k) {
-          float ms = 0.f;
-          GG_HIP(hipEventElapsedTime(&ms, mp_ev(j)[k], mp_ev(j)[k + 1]));
-          launch_ms[k] += ms;
-        }
-      float ms = 0.f;
-      GG_HIP(hipEventElapsedTime(&ms, sev.ev[steps], sev.ev[steps + 1]));
-      launch_ms[d] = ms;
-    }
-  }
-  int done = steps;
-  for (int j = 0; j < steps; ++j)
-    if (!(betas_host[j] > 1e-300)) {
-      done = j + 1;
-      break;
-    }
-  if (steps_done) *steps_done = done;
-}
-
-static void lanczos_probe(const gg_kron* K, double shift, uint64_t seed, int probe, int steps,
-                          double* work_dev, double* alphas_host, double* betas_host,
-                          int* steps_done, double* step_ms, double* launch_ms,
-                          gg_stream stream) {
-  {
-    GG_REQUIRE(K && work_dev && alphas_host && betas_host && steps >= 1, GG_ERR_VALUE,
-               "bad argument");
-    int64_t nr = 0, nc = 0, we = 0;
-    gg_kron_shape(K, 0, &nr, &nc, &we);
-    GG_REQUIRE(nr == nc, GG_ERR_VALUE, "Lanczos needs a square operator");
-    GG_REQUIRE(we <= nr, GG_ERR_VALUE, "non-square factors are not supported here");
-    if (lanczos_use_block(K)) {
-      lanczos_block(K, shift, seed, probe, steps, work_dev, alphas_host, betas_host, steps_done,
-                    step_ms, launch_ms, stream);
-      return;
-    }
-    hipStream_t s = gg::as_stream(stream);
-    const int64_t n = nr;
-    double* P = work_dev;        // u_prev (v_prev = sP u_prev)
-    double* V = work_dev + n;    // u      (v = sV u)
-    double* W = work_dev + 2 * n;
-    double* mvw = work_dev + 3 * n;
-    const int nb = gg::vec_blocks(n);
-    const int64_t npart = std::max<int64_t>(gg::kron_partials_needed(K, false), gg::kVecBlocks);
-    const int64_t nrr = std::max<int64_t>(gg::kron_prologue_blocks(K), 1);
-    // [alphas | betas | partials | |w|^2 partials | zero | dot | lzs(8)]
-    double* scal = nullptr;
-    GG_HIP(hipMallocAsync(&scal, (2 * (size_t)steps + npart + nrr + 10 + 8) * sizeof(double), s));
-    double* alphas = scal;
-    double* betas = scal + steps;
-    double* parts = scal + 2 * steps;
-    double* rrparts = parts + npart;
-    double* zero = rrparts + nrr;
-    double* dot = zero + 1;
-    double* lzs = dot + 1;
-    const double init[2] = {1.0, 0.0};   // sV = 1 (the probe is normalised), sP = 0
-    GG_HIP(hipMemsetAsync(zero, 0, sizeof(double), s));
-    GG_HIP(hipMemcpyAsync(lzs, init, sizeof(init), hipMemcpyHostToDevice, s));
-    GG_HIP(hipMemsetAsync(P, 0, n * sizeof(double), s));
-    hipLaunchKernelGGL(gg::probe_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s,
-                       gg::probe_base(seed, probe), 1.0 / std::sqrt((double)n), V, n);
-    GG_LAUNCH_CHECK();
-    const int d = gg::kron_d(K);
-    const bool timed = step_ms != nullptr;
-    // step boundaries, then the closing pass's end (ev[steps] -> ev[steps + 1];
-    // with the update fused, the last step's update pass is the closing one)
-    gg::EventSet sev(timed ? (size_t)steps + 2 : 0);
-    gg::EventSet mev(timed && launch_ms ? (size_t)steps * (d + 1) : 0);
-    auto mp_ev = [&](int j) -> hipEvent_t* {
-      return mev.ev.empty() ? nullptr : mev.ev.data() + (size_t)j * (d + 1);
-    };
-    if (timed) GG_HIP(hipEventRecord(sev.ev[0], s));
-    // w = cy W + cu u + cp u_prev in place of W, |w|^2 -> betas[j], scales
-    auto update_beta = [&](int j) {
-      const int wide = ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(V) |
-                         reinterpret_cast<uintptr_t>(P)) & 15) == 0;
-      hipLaunchKernelGGL(gg::lz_update_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, W, V, P, n,
-                         lzs, parts, wide);
-      GG_LAUNCH_CHECK();
-      gg::launch_reduce_to(parts, nb, betas + j, s);
-      hipLaunchKernelGGL(gg::lz_beta_kernel, dim3(1), dim3(1), 0, s, lzs, betas + j);
-      GG_LAUNCH_CHECK();
-    };
-    // The update of step j - 1 rides on step j's first mode product as its
-    // prologue (CGP 3: the MFMA operand is w itself, written over u_prev)
-    // when the chain's first step writes its scratch, not y (an even number
-    // of factors); otherwise it is its own streaming pass.
-    const bool fuse = gg::kron_d(K) % 2 == 0;
-    for (int j = 0; j < steps; ++j) {
-      int64_t np = 0;
-      if (j == 0 || !fuse) {
-        // W = K u + shift u, and u.W per block of the last mode product
-        gg::kron_apply(K, false, V, W, shift, mvw, parts, nullptr, s, &np, nullptr, 0, mp_ev(j));
-      } else {
-        gg::MpFuse lf;
-        lf.r = V;
-        lf.q_old = P;
-        lf.p_out = P;
-        lf.rr_part = rrparts;
-        lf.rr_cap = nrr;
-        int64_t pro_blocks = 0;
-        lf.pro_blocks = &pro_blocks;
-        lf.coef = lzs;
-        gg::kron_apply(K, false, W, W, shift, mvw, parts, nullptr, s, &np, &lf, 3, mp_ev(j));
-        GG_REQUIRE(pro_blocks > 0 && pro_blocks <= nrr, GG_ERR_RUNTIME,
-                   "Lanczos: no prologue launch recorded");
-        // |w|^2 of the prologue -> beta_{j-1}; w (now in P) is the new u
-        gg::launch_reduce_to(rrparts, pro_blocks, betas + (j - 1), s);
-        hipLaunchKernelGGL(gg::lz_beta_kernel, dim3(1), dim3(1), 0, s, lzs, betas + (j - 1));
-        GG_LAUNCH_CHECK();
-        std::swap(P, V);   // u_prev <- u, u <- w
-      }
-      gg::launch_reduce_to(parts, np, dot, s);
-      const double* beta_prev = (j == 0) ? zero : betas + (j - 1);
-      hipLaunchKernelGGL(gg::lz_coef_kernel, dim3(1), dim3(1), 0, s, lzs, dot, alphas + j,
-                         beta_prev);
-      GG_LAUNCH_CHECK();
-      const bool closing = fuse && j + 1 == steps;
-      if (!fuse || j + 1 == steps) {
-        if (timed && closing) GG_HIP(hipEventRecord(sev.ev[steps], s));
-        update_beta(j);
-        if (j + 1 < steps) {
-          // rotate: u_prev <- u, u <- w, the old u_prev buffer takes the next matvec
-          double* oldP = P;
-          P = V;
-          V = W;
-          W = oldP;
-        }
-      }
-      if (timed && !closing) GG_HIP(hipEventRecord(sev.ev[j + 1], s));
-    }
-    if (timed) GG_HIP(hipEventRecord(sev.ev[steps + 1], s));
-    GG_HIP(hipMemcpyAsync(alphas_host, alphas, steps * sizeof(double), hipMemcpyDeviceToHost,
-                          s));
-    GG_HIP(hipMemcpyAsync(betas_host, betas, steps * sizeof(double), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipFreeAsync(scal, s));
-    GG_HIP(hipStreamSynchronize(s));
-    if (timed) {
-      for (int j = 0; j < steps; ++j) {
-        float ms = 0.f;
-        GG_HIP(hipEventElapsedTime(&ms, sev.ev[j], sev.ev[j + 1]));
-        step_ms[j] = ms;
-      }
-      if (launch_ms) {
-        for (int k = 0; k < d; ++k) launch_ms[k] = 0.0;
-        for (int j = 0; j < steps; ++j)
-          for (int k = 0; k < d; ++k) {
-            float ms = 0.f;
-            GG_HIP(hipEventElapsedTime(&ms, mp_ev(j)[k], mp_ev(j)[k + 1]));
-            launch_ms[k] += ms;
-          }
-        float ms = 0.f;
-        GG_HIP(hipEventElapsedTime(&ms, sev.ev[steps], sev.ev[steps + 1]));
-        launch_ms[d] = ms;
-      }
-    }
-    int done = steps;
-    for (int j = 0; j < steps; ++j)
-      if (!(betas_host[j] > 1e-300)) {
-        done = j + 1;
-        break;
-      }
-    if (steps_done) *steps_done = done;
-  }
-}
-
-}  // namespace gg
-
-// ============================================ CG scalars for a host-driven (sharded) CG
-// The sharded solve (gp_grief_amd/distributed.py) runs the same recurrence as
-// gg_cg_*: local partial dots land in device doubles, the caller all-reduces
-// them with RCCL, and these kernels consume the global values.
-namespace gg {
-
-// q += shift p ; partial p.q -- 16-byte lanes when q and p are 16-byte
-// aligned (wide), else 8-byte
-__global__ __launch_bounds__(kVecThreads) void shift_dot_kernel(double* __restrict__ q,
-                                                                const double* __restrict__ p,
-                                                                int64_t n, double shift,
-                                                                const CgScalars* __restrict__ sc,
-                                                                double* __restrict__ partials,
-                                                                int wide) {
-  if (sc->done) return;
-  double acc = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (wide) {
-    const int64_t n2 = n / 2;
-    double2* q2 = reinterpret_cast<double2*>(q);
-    const double2* p2 = reinterpret_cast<const double2*>(p);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
-      const double2 pv = p2[i];
-      double2 v = q2[i];
-      v.x = fma(shift, pv.x, v.x);
-      v.y = fma(shift, pv.y, v.y);
-      q2[i] = v;
-      acc = fma(pv.x, v.x, acc);
-      acc = fma(pv.y, v.y, acc);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
-      const double v = fma(shift, p[n - 1], q[n - 1]);
-      q[n - 1] = v;
-      acc = fma(p[n - 1], v, acc);
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-      const double pv = p[i];
-      const double v = fma(shift, pv, q[i]);
-      q[i] = v;
-      acc = fma(pv, v, acc);
-    }
-  }
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-__global__ void cgs_init_kernel(CgScalars* sc, const double* rr, double rtol, double atol) {
-  const double s = *rr;
-  sc->rho = s;
-  sc->rho_prev = 0.0;
-  sc->bnorm = sqrt(s);
-  sc->tol = fmax(atol, rtol * sc->bnorm);
-  sc->iters = 0;
-  sc->first = 1;
-  sc->pending = 0;
-  sc->alpha = sc->beta = sc->pq = 0.0;
-  // the fused recurrence's state (unused by the textbook one)
-  sc->rq = sc->qq = 0.0;
-  sc->repair = 0;
-  sc->cancels = 0;
-  sc->xpend = 0;
-  sc->xh = 2;
-  sc->xs = 0;
-  sc->done = (s == 0.0 || !(sqrt(s) >= sc->tol)) ? 1 : 0;
-}
-
-// ---- fused sharded CG (gg_cgs_fused_*): the single-GPU fused recurrence
-// with the dot products reduced across ranks by ONE all-reduce of five
-// doubles per iteration, red = [r.r, p.q_old, p.q, 0, q.q] (the caller
-// all-reduces it between gg_cgs_fused_post and gg_cgs_fused_scalars)
-
-// block partials of p.q' and q'.q', q' = Y + shift p (Y = K p after the
-// exchanges, left unshifted: the next prologue adds shift p_old itself) --
-// two read streams, 16-byte lanes (n even, 16-byte aligned vectors)
-__global__ __launch_bounds__(kVecThreads) void cgs_post_kernel(
-    const double* __restrict__ q, const double* __restrict__ p, int64_t n, double shift,
-    const CgScalars* __restrict__ sc, double* __restrict__ part, int64_t pstride) {
-  if (sc->done) return;
-  double pq = 0.0, qq = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const double2* q2 = reinterpret_cast<const double2*>(q);
-  const double2* p2 = reinterpret_cast<const double2*>(p);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 2; i += stride) {
-    const double2 pv = p2[i];
-    double2 v = q2[i];
-    v.x = fma(shift, pv.x, v.x);
-    v.y = fma(shift, pv.y, v.y);
-    pq = fma(pv.x, v.x, pq);
-    pq = fma(pv.y, v.y, pq);
-    qq = fma(v.x, v.x, qq);
-    qq = fma(v.y, v.y, qq);
-  }
-  const double a = block_sum(pq);
-  __syncthreads();
-  const double b = block_sum(qq);
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = a;
-    part[pstride + blockIdx.x] = b;
-  }
-}
-
-// red = [sum rr_part[0, nrr), sum rr_part[cap, cap + nrr), sum pq, 0, sum qq]
-__global__ __launch_bounds__(1024) void cgs_fused_red_kernel(
-    const double* __restrict__ rr_part, int64_t nrr, int64_t cap,
-    const double* __restrict__ part, int64_t np, int64_t pstride, double* __restrict__ red) {
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t i = threadIdx.x; i < nrr; i += blockDim.x) {
-    a[0] += rr_part[i];
-    a[1] += rr_part[cap + i];
-  }
-  for (int64_t i = threadIdx.x; i < np; i += blockDim.x) {
-    a[2] += part[i];
-    a[3] += part[pstride + i];
-  }
-  double t[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    t[k] = block_sum(a[k]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    red[0] = t[0];
-    red[1] = t[1];
-    red[2] = t[2];
-    red[3] = 0.0;
-    red[4] = t[3];
-  }
-}
-
-// the closing pending update r -= alpha (q + shift p), partial r.r
-__global__ __launch_bounds__(kVecThreads) void cgs_close_r_kernel(
-    double* __restrict__ r, const double* __restrict__ q, const double* __restrict__ p, int64_t n,
-    double shift, const CgScalars* __restrict__ sc, double* __restrict__ partials) {
-  if (sc->done || !sc->pending) return;
-  const double a = sc->alpha;
-  double acc = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double rv = r[i] - a * fma(shift, p[i], q[i]);
-    r[i] = rv;
-    acc = fma(rv, rv, acc);
-  }
-  const double s = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// the closing textbook step (cg_rho_kernel's need_pending 1) from the global
-// r.r (all-reduced by the caller)
-__global__ void cgs_close_rho_kernel(CgScalars* sc, const double* rr) {
-  if (sc->done || !sc->pending) return;
-  const double s = *rr;
-  sc->rho_prev = sc->rho;
-  sc->rho = s;
-  sc->beta = s / sc->rho_prev;
-  sc->iters += 1;
-  sc->first = 0;
-  sc->pending = 0;
-  sc->repair = 0;
-  if (!(sqrt(s) >= sc->tol)) sc->done = 1;
-}
-
-__global__ void cgs_alpha_kernel(CgScalars* sc, const double* pq) {
-  if (sc->done) return;
-  sc->pq = *pq;
-  sc->alpha = sc->rho / *pq;
-}
-
-__global__ void cgs_rho_kernel(CgScalars* sc, const double* rr) {
-  if (sc->done) return;
-  const double s = *rr;
-  sc->rho_prev = sc->rho;
-  sc->rho = s;
-  sc->beta = s / sc->rho_prev;
-  sc->iters += 1;
-  sc->first = 0;
-  if (!(sqrt(s) >= sc->tol)) sc->done = 1;
-}
-
-}  // namespace gg
-
-struct gg_cgs {
-  gg::CgScalars* sc = nullptr;
-  gg::CgScalars* host = nullptr;
-  double* partials = nullptr;   // kVecBlocks, or 2 x kVecBlocks (fused post)
-  // fused recurrence: the prologue launch's r.r / p.q_old partials
-  // (2 x rr_cap) and its actual workgroup count
-  double* rr_part = nullptr;
-  int64_t rr_cap = 0;
-  int64_t pro_blocks = 0;
-};
-
-namespace gg {
-
-CgScalars* cgs_scalars_ptr(gg_cgs* c) { return c->sc; }
-
-// the prologue partial arrays for launches of up to `cap` workgroups (grown
-// on demand, zero-filled)
-double* cgs_rr_part(gg_cgs* c, int64_t cap, int64_t* cap_out) {
-  if (c->rr_cap < cap) {
-    if (c->rr_part) GG_HIP(hipFree(c->rr_part));
-    c->rr_part = nullptr;
-    GG_HIP(hipMalloc(&c->rr_part, 2 * (size_t)cap * sizeof(double)));
-    GG_HIP(hipMemset(c->rr_part, 0, 2 * (size_t)cap * sizeof(double)));
-    c->rr_cap = cap;
-  }
-  *cap_out = c->rr_cap;
-  return c->rr_part;
-}
-
-void cgs_set_pro_blocks(gg_cgs* c, int64_t nb) { c->pro_blocks = nb; }
-
-}  // namespace gg
-
-extern "C" {
-
-int gg_cgs_create(gg_cgs** out) {
-  return gg::guard([&] {
-    gg::knobs_reload();   // the handle's switches are the environment's now
-    GG_REQUIRE(out, GG_ERR_VALUE, "NULL argument");
-    gg_cgs* c = new gg_cgs();
-    try {
-      GG_HIP(hipMalloc(&c->sc, sizeof(gg::CgScalars)));
-      gg::scalars_clear(c->sc);
-      GG_HIP(hipHostMalloc(&c->host, sizeof(gg::CgScalars), hipHostMallocDefault));
-      GG_HIP(hipMalloc(&c->partials, 2 * gg::kVecBlocks * sizeof(double)));
-    } catch (...) {
-      gg_cgs_destroy(c);
-      throw;
-    }
-    *out = c;
-  });
-}
-
-int gg_cgs_destroy(gg_cgs* c) {
-  return gg::guard([&] {
-    if (!c) return;
-    if (c->sc) (void)hipFree(c->sc);
-    if (c->host) (void)hipHostFree(c->host);
-    if (c->partials) (void)hipFree(c->partials);
-    if (c->rr_part) (void)hipFree(c->rr_part);
-    delete c;
-  });
-}
-
-int gg_cgs_scalars(gg_cgs* c, void** scalars_dev) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && scalars_dev, GG_ERR_VALUE, "NULL argument");
-    *scalars_dev = c->sc;
-  });
-}
-
-int gg_cgs_local_dot(gg_cgs* c, const double* x_dev, const double* y_dev, int64_t n,
-                     double* out_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && x_dev && y_dev && out_dev, GG_ERR_VALUE, "NULL argument");
-    hipStream_t s = gg::as_stream(stream);
-    const int nb = gg::vec_blocks(n);
-    gg::launch_dot_partials(x_dev, y_dev, n, c->partials, nb, s);
-    gg::launch_reduce_to(c->partials, nb, out_dev, s);
-  });
-}
-
-int gg_cgs_init(gg_cgs* c, const double* rr_dev, double rtol, double atol, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && rr_dev && rtol >= 0 && atol >= 0, GG_ERR_VALUE, "bad argument");
-    hipLaunchKernelGGL(gg::cgs_init_kernel, dim3(1), dim3(1), 0, gg::as_stream(stream), c->sc,
-                       rr_dev, rtol, atol);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_cgs_shift_dot(gg_cgs* c, double* q_dev, const double* p_dev, int64_t n, double shift,
-                     double* out_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && q_dev && p_dev && out_dev, GG_ERR_VALUE, "NULL argument");
-    hipStream_t s = gg::as_stream(stream);
-    const int nb = gg::vec_blocks(n);
-    const int wide =
-        ((reinterpret_cast<uintptr_t>(q_dev) | reinterpret_cast<uintptr_t>(p_dev)) & 15) == 0;
-    hipLaunchKernelGGL(gg::shift_dot_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, q_dev,
-                       p_dev, n, shift, c->sc, c->partials, wide);
-    GG_LAUNCH_CHECK();
-    gg::launch_reduce_to(c->partials, nb, out_dev, s);
-  });
-}
-
-int gg_cgs_alpha(gg_cgs* c, const double* pq_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && pq_dev, GG_ERR_VALUE, "NULL argument");
-    hipLaunchKernelGGL(gg::cgs_alpha_kernel, dim3(1), dim3(1), 0, gg::as_stream(stream), c->sc,
-                       pq_dev);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_cgs_update(gg_cgs* c, double* x_dev, double* r_dev, const double* p_dev,
-                  const double* q_dev, int64_t n, double* out_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && x_dev && r_dev && p_dev && q_dev && out_dev, GG_ERR_VALUE, "NULL argument");
-    hipStream_t s = gg::as_stream(stream);
-    const int nb = gg::vec_blocks(n);
-    hipLaunchKernelGGL(gg::cg_xr_update_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, x_dev,
-                       r_dev, p_dev, q_dev, n, c->sc, c->partials, 0);
-    GG_LAUNCH_CHECK();
-    gg::launch_reduce_to(c->partials, nb, out_dev, s);
-  });
-}
-
-int gg_cgs_rho(gg_cgs* c, const double* rr_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && rr_dev, GG_ERR_VALUE, "NULL argument");
-    hipLaunchKernelGGL(gg::cgs_rho_kernel, dim3(1), dim3(1), 0, gg::as_stream(stream), c->sc,
-                       rr_dev);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_cgs_fused_post(gg_cgs* c, const double* q_dev, const double* p_dev, int64_t n,
-                      double shift, double* red_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && q_dev && p_dev && red_dev && n >= 2 && n % 2 == 0, GG_ERR_VALUE,
-               "bad argument");
-    GG_REQUIRE(((reinterpret_cast<uintptr_t>(q_dev) | reinterpret_cast<uintptr_t>(p_dev)) & 15) ==
-                   0,
-               GG_ERR_VALUE, "fused post needs 16-byte aligned vectors");
-    GG_REQUIRE(c->rr_part && c->pro_blocks > 0, GG_ERR_VALUE,
-               "gg_cgs_fused_post needs a fused phase 1 first");
-    hipStream_t s = gg::as_stream(stream);
-    const int nb = gg::vec_blocks(n);
-    hipLaunchKernelGGL(gg::cgs_post_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, q_dev, p_dev,
-                       n, shift, c->sc, c->partials, (int64_t)gg::kVecBlocks);
-    GG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gg::cgs_fused_red_kernel, dim3(1), dim3(1024), 0, s, c->rr_part,
-                       c->pro_blocks, c->rr_cap, c->partials, (int64_t)nb,
-                       (int64_t)gg::kVecBlocks, red_dev);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_cgs_fused_scalars(gg_cgs* c, const double* red_dev, const double* p_new_dev,
-                         gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && red_dev && p_new_dev, GG_ERR_VALUE, "NULL argument");
-    // red = [rr, p.q_old | p.q, (r.q), q.q]: the single-GPU scalars kernel
-    // with one-element partial arrays (rr stride 1, matvec stride 1)
-    hipLaunchKernelGGL(gg::cg_fused_scalars_kernel, dim3(1), dim3(1024), 0, gg::as_stream(stream),
-                       red_dev, (int64_t)1, (int64_t)1, red_dev + 2, (int64_t)1, (int64_t)1,
-                       c->sc, p_new_dev, 2, 1, 0);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_cgs_fused_close(gg_cgs* c, double* x_dev, double* r_dev, const double* q_dev,
-                       const double* p_dev, int64_t n, int64_t half, double shift,
-                       double* rr_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && x_dev && r_dev && q_dev && p_dev && rr_dev && half >= 0 && half <= n,
-               GG_ERR_VALUE, "bad argument");
-    hipStream_t s = gg::as_stream(stream);
-    const int nb = gg::vec_blocks(n);
-    // the deferred x steps, then the pending r update with its r.r partials
-    hipLaunchKernelGGL(gg::cg_x_flush2_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, x_dev, n,
-                       half, c->sc);
-    GG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gg::cg_x_flushed_kernel, dim3(1), dim3(1), 0, s, c->sc);
-    GG_LAUNCH_CHECK();
-    GG_HIP(hipMemsetAsync(c->partials, 0, nb * sizeof(double), s));
-    hipLaunchKernelGGL(gg::cgs_close_r_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, r_dev,
-                       q_dev, p_dev, n, shift, c->sc, c->partials);
-    GG_LAUNCH_CHECK();
-    gg::launch_reduce_to(c->partials, nb, rr_dev, s);
-  });
-}
-
-int gg_cgs_fused_close_rho(gg_cgs* c, const double* rr_dev, gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c && rr_dev, GG_ERR_VALUE, "NULL argument");
-    hipLaunchKernelGGL(gg::cgs_close_rho_kernel, dim3(1), dim3(1), 0, gg::as_stream(stream), c->sc,
-                       rr_dev);
-    GG_LAUNCH_CHECK();
-  });
-}
-
-int gg_cgs_status(gg_cgs* c, int* iters, int* done, double* rho, double* tol,
-                  gg_stream stream) {
-  return gg::guard([&] {
-    GG_REQUIRE(c, GG_ERR_VALUE, "NULL handle");
-    hipStream_t s = gg::as_stream(stream);
-    GG_HIP(hipMemcpyAsync(c->host, c->sc, sizeof(gg::CgScalars), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipStreamSynchronize(s));
-    if (iters) *iters = c->host->iters;
-    if (done) *done = c->host->done;
-    if (rho) *rho = c->host->rho;
-    if (tol) *tol = c->host->tol;
   });
 }
 

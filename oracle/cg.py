@@ -12,7 +12,7 @@ the scipy history stored in tests/golden/grid_gp.npz.
 slq_logdet is stochastic Lanczos quadrature for log det(A); no reference
 exists (parity unpinned), it is checked against the exact eigenvalue log-det.
 The Rademacher probes come from a counter hash that the HIP library computes
-identically (gp_grief_amd/csrc/gg_vec.hip, gg_probe_kernel), so CPU and GPU
+identically (gp_grief_amd/csrc/gg_diag.hip, probe_kernel), so CPU and GPU
 Lanczos run on the same probe vectors.
 """
 import numpy as np

@@ -285,7 +285,7 @@ def trace_ratio_bound(d, scales, chain=16):
 
 def trace_ratio_chain(ms, threads=2048 * 256, items_fill=131072, seg_min=16, seg_max=128):
     """The longest chain of additions one thread of gg_kron_trace_ratio runs
-    for the grid ms (its launch geometry, gg_vec.hip): segment length times
+    for the grid ms (its launch geometry, gg_diag.hip): segment length times
     grid-stride passes."""
     ml = int(ms[-1])
     nhead = int(np.prod(ms)) // ml
