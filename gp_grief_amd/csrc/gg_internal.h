@@ -80,6 +80,10 @@ inline void check_status(int st) {
 // ---- device scalar block shared by the Krylov drivers (CG / Lanczos) ----
 constexpr int kXWinMax = 8;       // x_defer mode 3: the largest window
 constexpr int kXWinDefault = 8;   // and the default (GG_CG_XWIN; profiles/r06/b_win)
+// the window's schedule in the pair launch (GG_CG_XWIN_PHASE): one streaming
+// phase per R units of a workgroup; 1 = one visit per unit (A/B)
+constexpr int kXWinPhaseMax = 8;
+constexpr int kXWinPhaseDefault = 8;
 struct CgScalars {
   double rho;       // r.r of the current residual
   double rho_prev;  // r.r of the previous residual
@@ -184,6 +188,7 @@ struct MpFuse {
   // armed in sc (sreg, scnt, scoef, sdir) over region sreg of xwin regions
   int xdefer = 0;
   int xwin = 0;
+  int xphase = 0;   // xdefer 3: units per window phase (0: the default)
   int64_t soff = 0;
   int64_t soff_h1 = 0, sn_h1 = 0;
   // output of the first mode product when the ping-pong would put it in y

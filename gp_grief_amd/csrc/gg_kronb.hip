@@ -965,7 +965,34 @@ struct PairArgs {
   // x_defer mode 3 (SIDE bit 4): the armed region sc->sreg of length sreg_len
   // (sn = the vector's length) gets x += sum_t sc->scoef[t] sc->sdir[t]
   int64_t sreg_len;
+  // the window's schedule: sphase <= 1 one visit per unit and wave slot (sstep
+  // as above); sphase = R >= 2 one streaming phase per R units of a workgroup
+  // -- sstep is then a UNIT's share of the region (a multiple of 16 doubles),
+  // workgroup b owns the shares of its units back to back, and its phases are
+  // staggered by (b / 8 + b / scus) % R
+  int sphase;
+  int scus;
 };
+
+// eight consecutive 64-bit words of the device scalar block through the
+// scalar cache (a phase's descriptor: read when the phase starts, not held in
+// registers across the slab products)
+__device__ __forceinline__ void sld8(const void* p, uint64_t (&v)[8]) {
+  asm volatile(
+      "s_load_dwordx2 %0, %8, 0x0\n\t"
+      "s_load_dwordx2 %1, %8, 0x8\n\t"
+      "s_load_dwordx2 %2, %8, 0x10\n\t"
+      "s_load_dwordx2 %3, %8, 0x18\n\t"
+      "s_load_dwordx2 %4, %8, 0x20\n\t"
+      "s_load_dwordx2 %5, %8, 0x28\n\t"
+      "s_load_dwordx2 %6, %8, 0x30\n\t"
+      "s_load_dwordx2 %7, %8, 0x38\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&s"(v[0]), "=&s"(v[1]), "=&s"(v[2]), "=&s"(v[3]), "=&s"(v[4]), "=&s"(v[5]),
+        "=&s"(v[6]), "=&s"(v[7])
+      : "s"(p)
+      : "memory");
+}
 
 // swizzle a double within 32-lane groups: lane (b4 b3 b2 b1 b0) reads lane
 // (b4, R1 R0, b1 b0) -- the 4-lane group R of its 16-lane row
@@ -1486,21 +1513,16 @@ __global__ __launch_bounds__(128 * SPW, 2) void blk_pair_lds_kernel(PairArgs A) 
   const double* sp1 = nullptr;
   double* sxo = nullptr;
   int64_t slen = 0;
-  // mode 3: the armed region, wcnt directions (wave-uniform)
-  double wcf[kXWinMax];
-  const double* wdir[kXWinMax];
+  // mode 3: the armed region at element woff, wcnt directions (wave-uniform);
+  // the coefficients and directions are read from A.sc where they are used
+  int64_t woff = 0;
   int wcnt = 0;
   if (SIDE & 4) {
     if (A.sc->warm && !A.sc->done) {
-      const int64_t off = (int64_t)A.sc->sreg * A.sreg_len;
-      slen = max((int64_t)0, min(A.sn - off, A.sreg_len));
+      woff = (int64_t)A.sc->sreg * A.sreg_len;
+      slen = max((int64_t)0, min(A.sn - woff, A.sreg_len));
       wcnt = A.sc->scnt;
-#pragma unroll
-      for (int t = 0; t < kXWinMax; ++t) {
-        wcf[t] = A.sc->scoef[t];
-        wdir[t] = A.sc->sdir[t] + off;
-      }
-      sxo = A.sx + off;
+      sxo = A.sx + woff;
     }
   } else if (SIDE & 1) {
     const int xh = A.sc->xh;
@@ -1551,6 +1573,16 @@ __global__ __launch_bounds__(128 * SPW, 2) void blk_pair_lds_kernel(PairArgs A) 
     const int64_t q0 = slot * A.sstep;
     const int64_t q1 = min(slen, q0 + A.sstep);
     constexpr int kWB = 4;
+    uint64_t dc[8], dd[8];
+    sld8(A.sc->scoef, dc);
+    sld8(A.sc->sdir, dd);
+    double wcf[kXWinMax];
+    const double* wdir[kXWinMax];
+#pragma unroll
+    for (int t = 0; t < kXWinMax; ++t) {
+      wcf[t] = __longlong_as_double((long long)dc[t]);
+      wdir[t] = reinterpret_cast<const double*>(dd[t]) + woff;
+    }
     for (int64_t e0 = q0 + 2 * lane; e0 < q1; e0 += kWB * 128) {
       double2 xv[kWB], a[kXWinMax][kWB];
 #pragma unroll
@@ -1585,6 +1617,110 @@ __global__ __launch_bounds__(128 * SPW, 2) void blk_pair_lds_kernel(PairArgs A) 
       }
     }
   };
+  // mode 3 in phases (A.sphase = R >= 2): every R-th unit of the workgroup,
+  // after GEMM 2, all of its waves stream the region shares [p0, p1) of the
+  // units since the last phase -- wave w takes the 128-double pieces w, w + NW,
+  // ... -- in one software-pipelined loop: D batches of 1 + WC 16-byte loads
+  // in flight, batch b + D issued as batch b is summed and stored.  The loop
+  // body has no branch (a lane past p1 re-reads the region's last pair and
+  // stores to the trash slot) and the batches keep their program order; the
+  // compiler still waits once per D batches (vmcnt(0) at the loop head, the
+  // gfx950 assembly), so the D batches issued during one turn of the loop
+  // are what is in flight at the next.  Each element's expression is
+  // side_chunk_win's.
+  auto win_phase = [&](auto wc_tag, int64_t p0, int64_t p1) {
+    constexpr int WC = decltype(wc_tag)::value;
+    constexpr int D = WC >= 6 ? 4 : WC >= 4 ? 6 : 8;
+    constexpr int64_t kStride = (int64_t)R::NW * 128;
+    uint64_t dc[8], dd[8];
+    sld8(A.sc->scoef, dc);
+    sld8(A.sc->sdir, dd);
+    double cf[WC];
+    const double* dir[WC];
+#pragma unroll
+    for (int t = 0; t < WC; ++t) {
+      cf[t] = __longlong_as_double((long long)dc[t]);
+      dir[t] = reinterpret_cast<const double*>(dd[t]) + woff;
+    }
+    const int64_t last = p1 - 2;   // p0 < p1, both even: the last pair
+    // the lane's offsets are formed here, not kept (or spilled) across the
+    // slab products: a spill reload inside the loop would drain the pipe
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    double* const trash = g_blk_trash + 2 * ln;
+    double2 xv[D], a[D][WC];
+    // batch at element eb (wave-uniform) into ring slot j
+    auto load = [&](int j, int64_t eb) {
+      const int64_t ebc = min(eb, last);
+      const uint32_t vo = (uint32_t)min((int64_t)(2 * ln), last - ebc) * 8u;
+      {
+        const gchar* b = reinterpret_cast<const gchar*>(
+            reinterpret_cast<uintptr_t>(ubase(sxo, ebc * 8)));
+        const gd2v v = *reinterpret_cast<const gd2*>(b + vo);
+        xv[j] = double2{v.x, v.y};
+      }
+#pragma unroll
+      for (int t = 0; t < WC; ++t) {
+        const gchar* b = reinterpret_cast<const gchar*>(
+            reinterpret_cast<uintptr_t>(ubase(dir[t], ebc * 8)));
+        const gd2v v = *reinterpret_cast<const gd2*>(b + vo);
+        a[j][t] = double2{v.x, v.y};
+      }
+      // batches stay in program order: the oldest loads are the first awaited
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto finish = [&](int j, int64_t eb) {
+      double2 s = {0.0, 0.0};
+#pragma unroll
+      for (int t = 0; t < WC; ++t) {
+        s.x += cf[t] * a[j][t].x;
+        s.y += cf[t] * a[j][t].y;
+      }
+      double2 o;
+      o.x = xv[j].x + s.x;
+      o.y = xv[j].y + s.y;
+      // unconditional: a lane past p1 stores to its trash slot
+      const int64_t e = eb + 2 * ln;
+      st2g(e + 1 < p1 ? sxo + e : trash, o);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    const int64_t e0 = p0 + (int64_t)wave * 128;
+#pragma unroll
+    for (int j = 0; j < D; ++j) load(j, e0 + j * kStride);
+#pragma unroll 1
+    for (int64_t eb = e0; eb < p1; eb += D * kStride) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        finish(j, eb + j * kStride);
+        load(j, eb + (j + D) * kStride);
+      }
+    }
+  };
+  auto win_phase_n = [&](int64_t p0, int64_t p1) {
+    if (p0 >= p1) return;
+    switch (wcnt) {
+      case 1: win_phase(std::integral_constant<int, 1>(), p0, p1); break;
+      case 2: win_phase(std::integral_constant<int, 2>(), p0, p1); break;
+      case 3: win_phase(std::integral_constant<int, 3>(), p0, p1); break;
+      case 4: win_phase(std::integral_constant<int, 4>(), p0, p1); break;
+      case 5: win_phase(std::integral_constant<int, 5>(), p0, p1); break;
+      case 6: win_phase(std::integral_constant<int, 6>(), p0, p1); break;
+      case 7: win_phase(std::integral_constant<int, 7>(), p0, p1); break;
+      case 8: win_phase(std::integral_constant<int, 8>(), p0, p1); break;
+      default: break;
+    }
+  };
+  // the phase schedule: this workgroup's units are ufirst .. ufirst + nmine - 1
+  // of the back-to-back order, pdone of them applied; a phase falls on the
+  // unit where the staggered counter wraps and on the last unit
+  const int wR = (SIDE & 4) ? A.sphase : 1;
+  int64_t ufirst = 0;
+  int pdone = 0, pctr = 0;
+  if ((SIDE & 4) && wR >= 2) {
+    const int64_t ub = nunit / G, ur = nunit % G;
+    ufirst = (int64_t)blockIdx.x * ub + min((int64_t)blockIdx.x, ur);
+    pctr = (int)((blockIdx.x / 8 + blockIdx.x / (unsigned)max(A.scus, 1)) % (unsigned)wR);
+  }
   PairSlabSrc cur = src_at(0);
 #pragma unroll
   for (int j = 0; j + 1 < NS; ++j) issue(cur, min(j, R::KS - 1), j);   // stages 0 .. NS - 2
@@ -1601,9 +1737,18 @@ __global__ __launch_bounds__(128 * SPW, 2) void blk_pair_lds_kernel(PairArgs A) 
     else
       pair_slab_lds<TF, SPW, EPI, JA, TF - JA, false, (SIDE & 2) != 0>(A, slab, sl, cslot, it == 0, cur, nxt, nv,
                                                       ring, issue, pq, qq);
-    if ((SIDE & 4) && slen > 0)
-      side_chunk_win(((int64_t)blockIdx.x + (int64_t)it * G) * R::NW + wave);
-    else if ((SIDE & 1) && slen > 0)
+    if ((SIDE & 4) && slen > 0) {
+      if (wR < 2) {
+        side_chunk_win(((int64_t)blockIdx.x + (int64_t)it * G) * R::NW + wave);
+      } else {
+        pctr = pctr + 1 == wR ? 0 : pctr + 1;
+        if (pctr == 0 || !nv) {
+          win_phase_n(min(slen, (ufirst + pdone) * A.sstep),
+                      min(slen, (ufirst + it + 1) * A.sstep));
+          pdone = it + 1;
+        }
+      }
+    } else if ((SIDE & 1) && slen > 0)
       side_chunk(((int64_t)blockIdx.x + (int64_t)it * G) * R::NW + wave);
     cslot = (cslot + R::KS) % NS;
     cur = nxt;
@@ -2139,8 +2284,17 @@ void block_apply(const BlockOp* B, const double* x, double* y, double shift, dou
     p.sx = cg->sx;
     p.sn = cg->sn;
     p.sreg_len = xwin_region(cg->sn, cg->xwin);
-    const int64_t slots = p.nslab / B->pair_spw * 2 * B->pair_spw;
-    p.sstep = 2 * ceil_div(std::max<int64_t>(p.sreg_len, 1), 2 * slots);
+    GG_REQUIRE(cg->sn % 2 == 0, GG_ERR_VALUE, "block CG: the x window takes x in pairs");
+    p.sphase = cg->xphase >= 1 && cg->xphase <= kXWinPhaseMax ? cg->xphase : kXWinPhaseDefault;
+    p.scus = B->cus;
+    const int64_t units = p.nslab / B->pair_spw;
+    if (p.sphase >= 2) {
+      // a unit's share: whole 128-byte lines of the region, the last clamped
+      p.sstep = 16 * ceil_div(std::max<int64_t>(p.sreg_len, 1), 16 * units);
+    } else {
+      const int64_t slots = units * 2 * B->pair_spw;
+      p.sstep = 2 * ceil_div(std::max<int64_t>(p.sreg_len, 1), 2 * slots);
+    }
   } else if (pair_side) {
     p.sc = cg->sc;
     p.sx = cg->sx;

@@ -648,6 +648,7 @@ struct gg_cg {
   // xwin + 1 direction buffers (slots 0..3 are p, p2, p3, p4 as created; the
   // rest lie past the scratch region) with the current direction at pcur
   int xwin = 0;
+  int xphase = 0;   // GG_CG_XWIN_PHASE latched at create (0: the default)
   int xmode = 0;
   double* ring[gg::kXWinMax + 1] = {};
   int pcur = 0;
@@ -714,6 +715,13 @@ static int cg_xwin_knob() {
   const char* e = knob("GG_CG_XWIN");
   const int k = e ? atoi(e) : kXWinDefault;
   return k < 2 ? 0 : std::min(k, kXWinMax);
+}
+// units per window phase of the pair launch (GG_CG_XWIN_PHASE, 1..8; 1: the
+// per-unit schedule, an A/B and test switch)
+static int cg_xphase_knob() {
+  const char* e = knob("GG_CG_XWIN_PHASE");
+  const int r = e ? atoi(e) : kXWinPhaseDefault;
+  return std::min(std::max(r, 1), kXWinPhaseMax);
 }
 // direction buffers beyond the four every handle has
 static int64_t cg_extra_dirs(int K) { return K >= 2 ? std::max(0, K + 1 - 4) : 0; }
@@ -852,6 +860,7 @@ int gg_cg_create_blocks(const gg_kron* K, int64_t blk0, int64_t nblk, double shi
       cg->p4 = work_dev + 5 * vs;
       cg->q2 = work_dev + 6 * vs;
       cg->xwin = gg::block_pair_side(B) ? gg::cg_xwin_knob() : 0;
+      cg->xphase = gg::cg_xphase_knob();
       cg->ring[0] = cg->p;
       cg->ring[1] = cg->p2;
       cg->ring[2] = cg->p3;
@@ -936,6 +945,7 @@ int gg_cg_create(const gg_kron* K, double shift, double* work_dev, gg_cg** out) 
         cg->basis = be ? (atoi(be) != 0 ? 1 : 0) : (gg::block_efficient(cg->blk) ? 1 : 0);
         // the window only where the pair launch carries the side job
         cg->xwin = gg::block_pair_side(cg->blk) ? xwin : 0;
+        cg->xphase = gg::cg_xphase_knob();
         for (int i = 0; i < gg::cg_extra_dirs(xwin); ++i)
           cg->ring[4 + i] = work_dev + extra_off + i * vs;
       } else {
@@ -1310,6 +1320,7 @@ int gg_cg_iterate_open(gg_cg* cg, int max_iters, int check_every, gg_stream stre
         fz.sn = n;
         fz.xdefer = xmode;
         fz.xwin = cg->xwin;
+    fz.xphase = cg->xphase;
         fz.rderive = cg->rder;
         fz.pprev = cg->rder ? cg->pprev_buf() : nullptr;
         fz.first_dst = cg->first_dst;
@@ -1504,6 +1515,7 @@ int gg_cg_iterate_partial(gg_cg* cg, double* red_dev, gg_stream stream) {
     fz.sn = n;
     fz.xdefer = xmode;
     fz.xwin = cg->xwin;
+    fz.xphase = cg->xphase;
     fz.rderive = cg->rder;
     fz.pprev = cg->rder ? cg->pprev_buf() : nullptr;
     fz.first_dst = cg->first_dst;

@@ -246,9 +246,13 @@ int gg_cg_get_xdefer(const gg_cg* cg, int* on);
  * x is cut into K regions and each iteration's pair launch brings ONE region
  * up to date with the (at most K) steps it has not seen, so x moves once per
  * K iterations and each direction once -- (K + 2) / K passes per iteration
- * instead of 2, with K + 1 direction buffers in work_dev.  Same iterates up to
- * rounding.  *K: the window in effect (once started; before, what gg_cg_start
- * will pick), 0 when x is updated otherwise.                              */
+ * instead of 2, with K + 1 direction buffers in work_dev (K + 5 vectors of n
+ * in all).  Same iterates up to rounding.  The pair launch applies the region
+ * in streaming phases, one per GG_CG_XWIN_PHASE (1..8, default 8, latched at
+ * create) units of a workgroup; 1 visits it once per unit (A/B, tests).  The
+ * schedule changes neither x (bitwise) nor the memory.  *K: the window in
+ * effect (once started; before, what gg_cg_start will pick), 0 when x is
+ * updated otherwise.                                                      */
 int gg_cg_get_xwin(const gg_cg* cg, int* K);
 /* With the window in the block basis the CG keeps no r in memory (round 6,
  * GG_CG_RDERIVE=0 at create keeps it): the prologue takes r_{j-1} = p_{j-1} -
