@@ -50,6 +50,37 @@ __global__ __launch_bounds__(kVecThreads) void shift_dot_kernel(double* __restri
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
+// x += alpha p ; r -= alpha q ; partial r.r one double at a time: gg_cgs_update
+// on operands that are only 8-byte aligned (cg_xr_update_kernel's 16-byte
+// lanes otherwise); the same expressions, so both paths round alike
+__global__ __launch_bounds__(kVecThreads) void cgs_xr_update_narrow_kernel(
+    double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+    const double* __restrict__ q, int64_t n, const CgScalars* __restrict__ sc,
+    double* __restrict__ partials) {
+  if (sc->done) return;
+  const double a = sc->alpha;
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    x[i] += a * p[i];
+    const double rv = r[i] - a * q[i];
+    r[i] = rv;
+    acc = fma(rv, rv, acc);
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// the block partials of a step that the done latch skips were not written:
+// its out_dev is 0 (what the caller's all-reduce then sums)
+__global__ __launch_bounds__(1024) void cgs_reduce_kernel(const double* __restrict__ partials,
+                                                          int64_t count,
+                                                          const CgScalars* __restrict__ sc,
+                                                          double* __restrict__ out) {
+  const double s = sc->done ? 0.0 : sum_partials(partials, count);
+  if (threadIdx.x == 0) *out = s;
+}
+
 __global__ void cgs_init_kernel(CgScalars* sc, const double* rr, double rtol, double atol) {
   const double s = *rr;
   sc->rho = s;
@@ -108,7 +139,10 @@ __global__ __launch_bounds__(kVecThreads) void cgs_post_kernel(
 // red = [sum rr_part[0, nrr), sum rr_part[cap, cap + nrr), sum pq, 0, sum qq]
 __global__ __launch_bounds__(1024) void cgs_fused_red_kernel(
     const double* __restrict__ rr_part, int64_t nrr, int64_t cap,
-    const double* __restrict__ part, int64_t np, int64_t pstride, double* __restrict__ red) {
+    const double* __restrict__ part, int64_t np, int64_t pstride,
+    const CgScalars* __restrict__ sc, double* __restrict__ red) {
+  // done: neither the prologue nor cgs_post_kernel wrote its partials
+  if (sc->done) nrr = np = 0;
   double a[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t i = threadIdx.x; i < nrr; i += blockDim.x) {
     a[0] += rr_part[i];
@@ -229,6 +263,7 @@ int gg_cgs_create(gg_cgs** out) {
       gg::scalars_clear(c->sc);
       GG_HIP(hipHostMalloc(&c->host, sizeof(gg::CgScalars), hipHostMallocDefault));
       GG_HIP(hipMalloc(&c->partials, 2 * gg::kVecBlocks * sizeof(double)));
+      GG_HIP(hipMemset(c->partials, 0, 2 * gg::kVecBlocks * sizeof(double)));
     } catch (...) {
       gg_cgs_destroy(c);
       throw;
@@ -259,6 +294,7 @@ int gg_cgs_local_dot(gg_cgs* c, const double* x_dev, const double* y_dev, int64_
                      double* out_dev, gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(c && x_dev && y_dev && out_dev, GG_ERR_VALUE, "NULL argument");
+    GG_REQUIRE(n >= 0, GG_ERR_VALUE, "n must not be negative");
     hipStream_t s = gg::as_stream(stream);
     const int nb = gg::vec_blocks(n);
     gg::launch_dot_partials(x_dev, y_dev, n, c->partials, nb, s);
@@ -279,13 +315,16 @@ int gg_cgs_shift_dot(gg_cgs* c, double* q_dev, const double* p_dev, int64_t n, d
                      double* out_dev, gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(c && q_dev && p_dev && out_dev, GG_ERR_VALUE, "NULL argument");
+    GG_REQUIRE(n >= 0, GG_ERR_VALUE, "n must not be negative");
     hipStream_t s = gg::as_stream(stream);
     const int nb = gg::vec_blocks(n);
     const int wide = gg::aligned16(q_dev) && gg::aligned16(p_dev);
     hipLaunchKernelGGL(gg::shift_dot_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, q_dev,
                        p_dev, n, shift, c->sc, c->partials, wide);
     GG_LAUNCH_CHECK();
-    gg::launch_reduce_to(c->partials, nb, out_dev, s);
+    hipLaunchKernelGGL(gg::cgs_reduce_kernel, dim3(1), dim3(1024), 0, s, c->partials,
+                       (int64_t)nb, c->sc, out_dev);
+    GG_LAUNCH_CHECK();
   });
 }
 
@@ -302,12 +341,20 @@ int gg_cgs_update(gg_cgs* c, double* x_dev, double* r_dev, const double* p_dev,
                   const double* q_dev, int64_t n, double* out_dev, gg_stream stream) {
   return gg::guard([&] {
     GG_REQUIRE(c && x_dev && r_dev && p_dev && q_dev && out_dev, GG_ERR_VALUE, "NULL argument");
+    GG_REQUIRE(n >= 0, GG_ERR_VALUE, "n must not be negative");
     hipStream_t s = gg::as_stream(stream);
     const int nb = gg::vec_blocks(n);
-    hipLaunchKernelGGL(gg::cg_xr_update_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, x_dev,
-                       r_dev, p_dev, q_dev, n, c->sc, c->partials, 0);
+    if (gg::aligned16(x_dev) && gg::aligned16(r_dev) && gg::aligned16(p_dev) &&
+        gg::aligned16(q_dev))
+      hipLaunchKernelGGL(gg::cg_xr_update_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, x_dev,
+                         r_dev, p_dev, q_dev, n, c->sc, c->partials, 0);
+    else
+      hipLaunchKernelGGL(gg::cgs_xr_update_narrow_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s,
+                         x_dev, r_dev, p_dev, q_dev, n, c->sc, c->partials);
     GG_LAUNCH_CHECK();
-    gg::launch_reduce_to(c->partials, nb, out_dev, s);
+    hipLaunchKernelGGL(gg::cgs_reduce_kernel, dim3(1), dim3(1024), 0, s, c->partials,
+                       (int64_t)nb, c->sc, out_dev);
+    GG_LAUNCH_CHECK();
   });
 }
 
@@ -336,7 +383,7 @@ int gg_cgs_fused_post(gg_cgs* c, const double* q_dev, const double* p_dev, int64
     GG_LAUNCH_CHECK();
     hipLaunchKernelGGL(gg::cgs_fused_red_kernel, dim3(1), dim3(1024), 0, s, c->rr_part,
                        c->pro_blocks, c->rr_cap, c->partials, (int64_t)nb,
-                       (int64_t)gg::kVecBlocks, red_dev);
+                       (int64_t)gg::kVecBlocks, c->sc, red_dev);
     GG_LAUNCH_CHECK();
   });
 }
@@ -358,7 +405,8 @@ int gg_cgs_fused_close(gg_cgs* c, double* x_dev, double* r_dev, const double* q_
                        const double* p_dev, int64_t n, int64_t half, double shift,
                        double* rr_dev, gg_stream stream) {
   return gg::guard([&] {
-    GG_REQUIRE(c && x_dev && r_dev && q_dev && p_dev && rr_dev && half >= 0 && half <= n,
+    GG_REQUIRE(c && x_dev && r_dev && q_dev && p_dev && rr_dev && n >= 0 && half >= 0 &&
+                   half <= n,
                GG_ERR_VALUE, "bad argument");
     hipStream_t s = gg::as_stream(stream);
     const int nb = gg::vec_blocks(n);

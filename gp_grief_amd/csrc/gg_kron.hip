@@ -1453,6 +1453,7 @@ int gg_kron_dist_create(int d, const int64_t* m, const double* const* factors_ho
       D->f.resize(d);
       for (int k = 0; k < d; ++k) {
         GG_REQUIRE(m[k] >= 1 && m[k] <= 256, GG_ERR_VALUE, "factor size must be in [1, 256]");
+        GG_REQUIRE(factors_host[k], GG_ERR_VALUE, "NULL factor");
         gg::pack_fragments(factors_host[k], m[k], m[k], false, D->f[k]);
         gg::pack_fold(factors_host[k], m[k], false, D->f[k]);
         D->n *= m[k];
@@ -1504,6 +1505,9 @@ int gg_kron_dist_set_peers(gg_kron_dist* D, double* own_xbuf, int use_ipc, const
                "peer handles / pointers required");
     GG_REQUIRE(D->peers_recv == nullptr, GG_ERR_VALUE, "peers already set");
     const int G = D->world;
+    if (!use_ipc)
+      for (int g = 0; g < G; ++g)
+        GG_REQUIRE(g == D->rank || ptrs[g] != nullptr, GG_ERR_VALUE, "NULL peer pointer");
     std::vector<double*> recv(G), out(G);
     for (int g = 0; g < G; ++g) {
       double* base = nullptr;

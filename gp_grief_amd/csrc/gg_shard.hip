@@ -144,6 +144,7 @@ int gg_shard0_fold(int d, const int64_t* m, int world, int rank, int inverse,
     GG_REQUIRE(m && in_dev && out_dev, GG_ERR_VALUE, "NULL argument");
     GG_REQUIRE(d >= 1 && world >= 1 && rank >= 0 && rank < world, GG_ERR_VALUE,
                "bad argument");
+    for (int k = 0; k < d; ++k) GG_REQUIRE(m[k] >= 1, GG_ERR_VALUE, "bad factor order");
     GG_REQUIRE(m[0] % world == 0, GG_ERR_VALUE, "factor 0's order must divide by the ranks");
     int64_t rest = 1;
     for (int k = 1; k < d; ++k) rest *= m[k];

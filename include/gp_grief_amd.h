@@ -348,7 +348,8 @@ int gg_cg_create_blocks(const gg_kron* K, int64_t blk0, int64_t nblk, double shi
  * gg_shard0_fold -- factor 0's row blocks (the transpose decomposition;
  * layout (m_1 .. m_{d-1}, a), a = i_0 - rank m_0 / world fastest): forward
  * out = the rank's elements of the grid vector in; inverse writes them back
- * into the grid vector out (its other elements untouched).                */
+ * into the grid vector out (its other elements untouched).  Both calls
+ * refuse a factor order below 1 in any position.                           */
 int gg_parity_fold(int d, const int64_t* m, int world, int rank, int inverse,
                    const double* in_dev, double* out_dev, gg_stream stream);
 int gg_shard0_fold(int d, const int64_t* m, int world, int rank, int inverse,
@@ -780,7 +781,20 @@ int gg_kron_dist_phase2_push(const gg_kron_dist* D, gg_stream stream);
 
 /* Device CG scalars for a host-driven (sharded) CG: the same recurrence as
  * gg_cg_*, with each global dot product all-reduced by the caller between the
- * kernels that produce the local value (out_dev) and consume it.             */
+ * kernels that produce the local value (out_dev) and consume it.
+ * n >= 0 everywhere (n == 0: no vector is touched and out_dev is 0).
+ * Alignment: gg_cgs_local_dot needs 16-byte aligned vectors and refuses
+ * others; gg_cgs_shift_dot and gg_cgs_update take vectors that are only
+ * 8-byte aligned (any operand off a 16-byte boundary selects their
+ * one-double kernels at run time).  out_dev, rr_dev, pq_dev: one double.
+ * The done latch: gg_cgs_init sets it for r.r == 0, NaN or negative and for
+ * sqrt(r.r) < tol, gg_cgs_rho (and the fused scalars / close_rho) once
+ * sqrt(r.r) < tol or NaN.  From then on every step but gg_cgs_init,
+ * gg_cgs_local_dot and gg_cgs_status is skipped: no vector and no scalar
+ * changes, and a skipped gg_cgs_shift_dot, gg_cgs_update, gg_cgs_fused_close
+ * writes 0 to its out_dev, a skipped gg_cgs_fused_post five zeros to red_dev
+ * (what the caller's all-reduce then sums).  gg_cgs_fused_close still applies
+ * the x steps the fused recurrence deferred before the latch was set.        */
 typedef struct gg_cgs gg_cgs;
 int gg_cgs_create(gg_cgs** out);
 int gg_cgs_destroy(gg_cgs* c);
@@ -807,7 +821,9 @@ int gg_cgs_status(gg_cgs* c, int* iters, int* done, double* rho, double* tol,
  * push epilogue; push != 0: scratch as in phase1_push), the exchanges and
  * phase 2 as for the textbook CG (K p lands in q), gg_cgs_fused_post (reads
  * only: p.(q + s p) and |q + s p|^2; writes red[5] = [r.r, p_new.q_old',
- * p.q', 0, q'.q'] local, q' = q + s p), the caller's all-reduce of red,
+ * p.q', 0, q'.q'] local, q' = q + s p; red[0] is 0 when the prologue had no
+ * pending update to apply -- the scalars then keep their rho -- and red[1]
+ * is 0 on the first step), the caller's all-reduce of red,
  * gg_cgs_fused_scalars (alpha, beta by the |r - alpha q'|^2 expansion with
  * r.q' = p.q' - beta p.q_old', the x deferral).  Leaving the iterations:
  * gg_cgs_fused_close (deferred x steps, pending r -= alpha (q + s p) with p

@@ -36,12 +36,13 @@ import oracle
 from oracle import cg as ocg
 from oracle import kron as okron
 
+from abi_guard import Guard, bits
+
 pytestmark = pytest.mark.gpu
 
 LD = np.longdouble
 U = 2.0 ** -53
 GG_OK, GG_ERR_VALUE = 0, -1
-GUARD = 64
 
 
 def rel(a, b):
@@ -50,59 +51,10 @@ def rel(a, b):
     return float(np.sqrt(np.sum((a - b) ** 2)) / max(np.sqrt(np.sum(b ** 2)), LD(1e-300)))
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
 @pytest.fixture(scope="module")
 def nat(gpu):
     from gp_grief_amd import native
     return native
-
-
-class Guard(object):
-    """n doubles on the device between two guards of 64 NaN doubles, the
-    payload `off` doubles past a 16-byte boundary (off = 1: 8-byte aligned
-    only).  data None: the payload is NaN too (an output, or scratch)."""
-
-    def __init__(self, n, data=None, off=0):
-        import torch
-        self.n, self.off = int(n), int(off)
-        self.lo = self.off + GUARD
-        h = np.full(self.lo + self.n + GUARD, np.nan)
-        if data is not None:
-            h[self.lo:self.lo + self.n] = np.asarray(data, dtype=np.float64).reshape(-1)
-        self.h0 = h
-        self.d = torch.from_numpy(h.copy()).cuda()
-        assert self.d.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return ctypes.c_void_p(self.d.data_ptr() + 8 * self.lo)
-
-    def _host(self):
-        import torch
-        torch.cuda.synchronize()
-        return self.d.cpu().numpy()
-
-    def read(self):
-        """The payload; asserts both guards bit for bit."""
-        flat = self._host()
-        a, b = bits(flat).copy(), bits(self.h0).copy()
-        a[self.lo:self.lo + self.n] = 0
-        b[self.lo:self.lo + self.n] = 0
-        assert np.array_equal(a, b), "a guard was written"
-        return flat[self.lo:self.lo + self.n].copy()
-
-    def unchanged(self):
-        """Asserts guards and payload bit for bit as they were made."""
-        assert np.array_equal(bits(self._host()), bits(self.h0)), "the buffer was written"
-
-    def reset(self):
-        import torch
-        torch.cuda.synchronize()
-        self.d.copy_(torch.from_numpy(self.h0))
-        torch.cuda.synchronize()
 
 
 def null_or(g):
