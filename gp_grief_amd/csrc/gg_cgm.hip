@@ -19,6 +19,15 @@
 // Preconditioned (gg_cgm_set_precond): z = Q diag(1 / (lam + s)) Q^T r from the
 // per-factor eigenpairs of K -- two more Kronecker matvecs, a decoded divide
 // and the dot r.z per iteration; the direction kernel applies W (u = z).
+//
+// Per-point noise (gg_cgm_set_noise): A = W K W + D, D = diag(noise).  The
+// matvec runs with shift 0, so its epilogue yields p.K p; the direction pass
+// also reads noise and emits partials of sum_i noise_i p_i^2 (its own region of
+// the partials buffer, past the matvec's), the alpha kernel sums both sets and
+// the update pass uses select(mask, t_i + noise_i p_i, 0): two more reads of N
+// doubles per iteration, no more launches.  noise at the missing points is
+// dropped by select (it may be NaN there).  `shift` then only feeds the
+// preconditioner.
 #include <cmath>
 #include <vector>
 
@@ -161,6 +170,109 @@ __global__ __launch_bounds__(kVecThreads) void cgm_direction_kernel(
   }
 }
 
+// per-point noise: x += alpha p ; r -= alpha select(mask, t + noise p, 0) ;
+// partial r.r
+template <bool V2>
+__global__ __launch_bounds__(kVecThreads) void cgm_xr_update_noise_kernel(
+    double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
+    const double* __restrict__ t, const double* __restrict__ noise,
+    const uint8_t* __restrict__ mask, int64_t n, const CgmScalars* __restrict__ sc,
+    double* __restrict__ partials) {
+  if (sc->done) return;
+  const double a = sc->alpha;
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (V2) {
+    const int64_t n2 = n / 2;
+    double2* x2 = reinterpret_cast<double2*>(x);
+    double2* r2 = reinterpret_cast<double2*>(r);
+    const double2* p2 = reinterpret_cast<const double2*>(p);
+    const double2* t2 = reinterpret_cast<const double2*>(t);
+    const double2* d2 = reinterpret_cast<const double2*>(noise);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+      const double2 pv = p2[i], tv = t2[i], dv = d2[i];
+      double2 xv = x2[i], rv = r2[i];
+      xv.x = fma(a, pv.x, xv.x);
+      xv.y = fma(a, pv.y, xv.y);
+      rv.x = fma(-a, sel(mask[2 * i], fma(dv.x, pv.x, tv.x)), rv.x);
+      rv.y = fma(-a, sel(mask[2 * i + 1], fma(dv.y, pv.y, tv.y)), rv.y);
+      x2[i] = xv;
+      r2[i] = rv;
+      acc = fma(rv.x, rv.x, acc);
+      acc = fma(rv.y, rv.y, acc);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+      const int64_t i = n - 1;
+      x[i] = fma(a, p[i], x[i]);
+      const double rv = fma(-a, sel(mask[i], fma(noise[i], p[i], t[i])), r[i]);
+      r[i] = rv;
+      acc = fma(rv, rv, acc);
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      x[i] = fma(a, p[i], x[i]);
+      const double rv = fma(-a, sel(mask[i], fma(noise[i], p[i], t[i])), r[i]);
+      r[i] = rv;
+      acc = fma(rv, rv, acc);
+    }
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// per-point noise: p = select(mask, u, 0) + beta p (p = select(mask, u, 0) on
+// the first iteration) and the partials of sum_i noise_i p_i^2, noise selected
+// by the mask.  V2: 16-byte lanes on noise (p and u are workspace vectors,
+// always 16-byte aligned); every block writes its partial.
+template <bool V2>
+__global__ __launch_bounds__(kVecThreads) void cgm_direction_noise_kernel(
+    double* __restrict__ p, const double* __restrict__ u, const double* __restrict__ noise,
+    const uint8_t* __restrict__ mask, int64_t n, const CgmScalars* __restrict__ sc,
+    double* __restrict__ partials) {
+  if (sc->done) return;
+  const bool first = sc->first != 0;
+  const double beta = sc->beta;
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (V2) {
+    const int64_t n2 = n / 2;
+    double2* p2 = reinterpret_cast<double2*>(p);
+    const double2* u2 = reinterpret_cast<const double2*>(u);
+    const double2* d2 = reinterpret_cast<const double2*>(noise);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+      const uint8_t m0 = mask[2 * i], m1 = mask[2 * i + 1];
+      const double2 dv = d2[i];
+      double2 uv = u2[i];
+      uv.x = sel(m0, uv.x);
+      uv.y = sel(m1, uv.y);
+      if (!first) {
+        const double2 pv = p2[i];
+        uv.x = fma(beta, pv.x, uv.x);
+        uv.y = fma(beta, pv.y, uv.y);
+      }
+      p2[i] = uv;
+      acc = fma(sel(m0, dv.x) * uv.x, uv.x, acc);
+      acc = fma(sel(m1, dv.y) * uv.y, uv.y, acc);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+      const int64_t i = n - 1;
+      const uint8_t m = mask[i];
+      const double uv = first ? sel(m, u[i]) : fma(beta, p[i], sel(m, u[i]));
+      p[i] = uv;
+      acc = fma(sel(m, noise[i]) * uv, uv, acc);
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      const uint8_t m = mask[i];
+      const double uv = first ? sel(m, u[i]) : fma(beta, p[i], sel(m, u[i]));
+      p[i] = uv;
+      acc = fma(sel(m, noise[i]) * uv, uv, acc);
+    }
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 // |W b|^2 -> tolerances, counters; unpreconditioned: rho = r.r
 __global__ __launch_bounds__(1024) void cgm_init_kernel(const double* __restrict__ partials,
                                                         int64_t count, CgmScalars* sc,
@@ -187,6 +299,21 @@ __global__ __launch_bounds__(1024) void cgm_alpha_kernel(const double* __restric
   if (threadIdx.x == 0) {
     sc->pq = s;
     sc->alpha = sc->rho / s;
+  }
+}
+
+// per-point noise: alpha = rho / (p.K p + sum_i noise_i p_i^2), the matvec's
+// partials and the direction pass's
+__global__ __launch_bounds__(1024) void cgm_alpha_noise_kernel(
+    const double* __restrict__ partials, int64_t count, const double* __restrict__ npartials,
+    int64_t ncount, CgmScalars* sc) {
+  if (sc->done) return;
+  const double s = sum_partials(partials, count);
+  __syncthreads();   // block_sum's shared scratch is reused
+  const double d = sum_partials(npartials, ncount);
+  if (threadIdx.x == 0) {
+    sc->pq = s + d;
+    sc->alpha = sc->rho / sc->pq;
   }
 }
 
@@ -242,7 +369,11 @@ struct gg_cgm {
   // by gg_cgm_set_precond: an unpreconditioned solve does not pay for them)
   double *zu = nullptr, *z = nullptr, *u = nullptr;
   int64_t mv_work_elems = 0;
-  double* partials = nullptr;          // device, max(kVecBlocks, matvec partials)
+  // device: max(kVecBlocks, matvec partials), then kVecBlocks more for the
+  // direction pass's noise partials (npartials)
+  double* partials = nullptr;
+  double* npartials = nullptr;
+  const double* noise = nullptr;       // per-point noise (gg_cgm_set_noise), or NULL
   gg::CgmScalars* sc = nullptr;        // device
   gg::CgmScalars* sc_host = nullptr;   // pinned mirror
   double* x = nullptr;
@@ -318,7 +449,8 @@ int gg_cgm_create(const gg_kron* K, double shift, const uint8_t* mask_dev, doubl
       c->mv_work_elems = gg::kron_work_elems(K, false);
       const int64_t np =
           std::max<int64_t>(gg::kVecBlocks, gg::kron_partials_needed(K, false));
-      GG_HIP(hipMalloc(&c->partials, np * sizeof(double)));
+      GG_HIP(hipMalloc(&c->partials, (np + gg::kVecBlocks) * sizeof(double)));
+      c->npartials = c->partials + np;
       GG_HIP(hipMalloc(&c->sc, sizeof(gg::CgmScalars)));
       GG_HIP(hipMemset(c->sc, 0, sizeof(gg::CgmScalars)));
       GG_HIP(hipHostMalloc(&c->sc_host, sizeof(gg::CgmScalars), hipHostMallocDefault));
@@ -362,6 +494,16 @@ int gg_cgm_set_precond(gg_cgm* c, const gg_kron* Q, const double* lam_dev) {
   });
 }
 
+int gg_cgm_set_noise(gg_cgm* c, const double* noise_dev) {
+  return gg::guard([&] {
+    GG_REQUIRE(c, GG_ERR_VALUE, "NULL handle");
+    GG_REQUIRE(c->x == nullptr, GG_ERR_VALUE, "set the noise before gg_cgm_start");
+    GG_REQUIRE((reinterpret_cast<uintptr_t>(noise_dev) & 7) == 0, GG_ERR_VALUE,
+               "the noise must hold doubles (8-byte aligned)");
+    c->noise = noise_dev;
+  });
+}
+
 int gg_cgm_start(gg_cgm* c, const double* b_dev, double* x_dev, double rtol, double atol,
                  gg_stream stream) {
   return gg::guard([&] {
@@ -400,17 +542,42 @@ int gg_cgm_iterate(gg_cgm* c, int max_iters, int check_every, gg_stream stream) 
     const bool pre = c->Q != nullptr;
     const bool x16 = gg::aligned16(c->x);
     if (check_every <= 0) check_every = max_iters;
+    const double* dn = c->noise;
+    const bool d16 = gg::aligned16(dn);
     for (int it = 0; it < max_iters; ++it) {
-      hipLaunchKernelGGL(gg::cgm_direction_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s, c->p,
-                         pre ? c->u : c->r, pre ? c->mask : (const uint8_t*)nullptr, n, c->sc);
+      if (dn == nullptr)
+        hipLaunchKernelGGL(gg::cgm_direction_kernel, dim3(nb), dim3(gg::kVecThreads), 0, s,
+                           c->p, pre ? c->u : c->r, pre ? c->mask : (const uint8_t*)nullptr, n,
+                           c->sc);
+      else if (d16)
+        hipLaunchKernelGGL(gg::cgm_direction_noise_kernel<true>, dim3(nb),
+                           dim3(gg::kVecThreads), 0, s, c->p, pre ? c->u : c->r, dn, c->mask, n,
+                           c->sc, c->npartials);
+      else
+        hipLaunchKernelGGL(gg::cgm_direction_noise_kernel<false>, dim3(nb),
+                           dim3(gg::kVecThreads), 0, s, c->p, pre ? c->u : c->r, dn, c->mask, n,
+                           c->sc, c->npartials);
       GG_LAUNCH_CHECK();
       int64_t nparts = 0;
-      gg::kron_apply(c->K, false, c->p, c->t, c->shift, c->mv_work, c->partials, &c->sc->done,
-                     s, &nparts, nullptr, 0, nullptr);
-      hipLaunchKernelGGL(gg::cgm_alpha_kernel, dim3(1), dim3(1024), 0, s, c->partials, nparts,
-                         c->sc);
+      gg::kron_apply(c->K, false, c->p, c->t, dn ? 0.0 : c->shift, c->mv_work, c->partials,
+                     &c->sc->done, s, &nparts, nullptr, 0, nullptr);
+      if (dn == nullptr)
+        hipLaunchKernelGGL(gg::cgm_alpha_kernel, dim3(1), dim3(1024), 0, s, c->partials, nparts,
+                           c->sc);
+      else
+        hipLaunchKernelGGL(gg::cgm_alpha_noise_kernel, dim3(1), dim3(1024), 0, s, c->partials,
+                           nparts, c->npartials, (int64_t)nb, c->sc);
       GG_LAUNCH_CHECK();
-      if (x16)
+      if (dn != nullptr) {
+        if (x16 && d16)
+          hipLaunchKernelGGL(gg::cgm_xr_update_noise_kernel<true>, dim3(nb),
+                             dim3(gg::kVecThreads), 0, s, c->x, c->r, c->p, c->t, dn, c->mask, n,
+                             c->sc, c->partials);
+        else
+          hipLaunchKernelGGL(gg::cgm_xr_update_noise_kernel<false>, dim3(nb),
+                             dim3(gg::kVecThreads), 0, s, c->x, c->r, c->p, c->t, dn, c->mask, n,
+                             c->sc, c->partials);
+      } else if (x16)
         hipLaunchKernelGGL(gg::cgm_xr_update_kernel<true>, dim3(nb), dim3(gg::kVecThreads), 0,
                            s, c->x, c->r, c->p, c->t, c->mask, n, c->sc, c->partials);
       else

@@ -184,6 +184,48 @@ __global__ __launch_bounds__(kVecThreads) void sample_residual_kernel(
   }
 }
 
+// per-point noise: b = select(mask, y - f - sqrt(noise) z, 0); noise at a
+// missing point is selected away like y (NaN allowed); wide also needs noise
+// 16-byte aligned
+__global__ __launch_bounds__(kVecThreads) void sample_residual_noise_kernel(
+    const double* __restrict__ y, const double* __restrict__ f,
+    const double* __restrict__ noise, const uint8_t* __restrict__ mask, uint64_t base,
+    double* __restrict__ b, int64_t n, int wide) {
+  const int64_t np = (n + 1) / 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < np; j += stride) {
+    const int64_t i = 2 * j;
+    const bool two = i + 1 < n;
+    double y0, y1 = 0.0, f0, f1 = 0.0, d0, d1 = 0.0;
+    if (wide && two) {
+      const double2 yv = reinterpret_cast<const double2*>(y)[j];
+      const double2 fv = reinterpret_cast<const double2*>(f)[j];
+      const double2 dv = reinterpret_cast<const double2*>(noise)[j];
+      y0 = yv.x;
+      y1 = yv.y;
+      f0 = fv.x;
+      f1 = fv.y;
+      d0 = dv.x;
+      d1 = dv.y;
+    } else {
+      y0 = y[i];
+      f0 = f[i];
+      d0 = noise[i];
+      if (two) {
+        y1 = y[i + 1];
+        f1 = f[i + 1];
+        d1 = noise[i + 1];
+      }
+    }
+    const bool o0 = mask == nullptr || mask[i] != 0;
+    const bool o1 = two && (mask == nullptr || mask[i + 1] != 0);
+    double z0, z1;
+    normal_pair(base, j, z0, z1);
+    store_pair(b, j, n, wide, o0 ? y0 - f0 - sqrt(d0) * z0 : 0.0,
+               o1 ? y1 - f1 - sqrt(d1) * z1 : 0.0);
+  }
+}
+
 // draw number k of Welford's running moments
 __device__ __forceinline__ void welford(double x, int k, double inv_k, double& mean, double& m2) {
   if (k == 1) {
@@ -322,6 +364,24 @@ int gg_sample_residual(const double* y_dev, const double* f_dev, const uint8_t* 
     hipLaunchKernelGGL(gg::sample_residual_kernel, dim3(gg::pair_blocks(n)),
                        dim3(gg::kVecThreads), 0, gg::as_stream(s), y_dev, f_dev, mask_dev,
                        noise_sd, gg::normal_base(seed, stream), b_dev, n, wide);
+    GG_LAUNCH_CHECK();
+  });
+}
+
+int gg_sample_residual_noise(const double* y_dev, const double* f_dev, const double* noise_dev,
+                             const uint8_t* mask_dev, uint64_t seed, int stream, double* b_dev,
+                             int64_t n, gg_stream s) {
+  return gg::guard([&] {
+    GG_REQUIRE(y_dev && f_dev && noise_dev && b_dev && n >= 0, GG_ERR_VALUE, "bad argument");
+    gg::require_stream(stream);
+    if (n == 0) return;
+    const int wide = gg::aligned16(y_dev) && gg::aligned16(f_dev) && gg::aligned16(noise_dev) &&
+                             gg::aligned16(b_dev)
+                         ? 1
+                         : 0;
+    hipLaunchKernelGGL(gg::sample_residual_noise_kernel, dim3(gg::pair_blocks(n)),
+                       dim3(gg::kVecThreads), 0, gg::as_stream(s), y_dev, f_dev, noise_dev,
+                       mask_dev, gg::normal_base(seed, stream), b_dev, n, wide);
     GG_LAUNCH_CHECK();
   });
 }

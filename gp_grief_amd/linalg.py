@@ -25,6 +25,9 @@ Device solvers (no reference implementation exists):
                    grid (gg_sample.hip): one Kronecker matvec per draw in the
                    eigenbasis on a complete grid, Matheron's rule (one CG
                    solve per draw) with a mask or the CG solver.
+Every one of the masked solvers takes noise=: per-point noise variances, the
+system W K W + diag(noise) (gg_cgm_set_noise, gg_lanczos_probe_masked_noise,
+gg_sample_residual_noise).
 """
 import ctypes
 import logging
@@ -292,6 +295,40 @@ def _mask_to_device(mask, n):
     return m, n_obs
 
 
+def _is_device_doubles(x):
+    """A contiguous float64 device tensor: usable where it lies."""
+    from . import device as dev
+    t = dev.torch()
+    return isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.float64 and x.is_contiguous()
+
+
+def _noise_to_device(noise, n, mask_dev=None, check=True):
+    """(n float64 device doubles, geometric mean over the observed points) of a
+    per-point noise vector, numpy or device; a contiguous float64 device
+    tensor is used where it lies (any 8-byte alignment).  Refuses a value that
+    is not positive and finite at an observed point (one device reduction);
+    at the missing points it is not looked at (NaN allowed).  check=False: no
+    reduction and no mean (None)."""
+    from . import device as dev
+    t = dev.torch()
+    nd = noise.detach().reshape(-1) if _is_device_doubles(noise) else dev.to_device(noise)
+    if nd.numel() != n:
+        raise ValueError("noise must have %d entries, not %d" % (n, nd.numel()))
+    if not check:
+        return nd, None
+    seen = nd if mask_dev is None else t.where(mask_dev != 0, nd, t.ones_like(nd))
+    if not bool(((seen > 0) & t.isfinite(seen)).all().item()):
+        raise ValueError("noise must be positive and finite at every observed point")
+    count = n if mask_dev is None else int((mask_dev != 0).sum().item())
+    return nd, float(t.exp(t.log(seen).sum() / count).item())
+
+
+def _all_ones_mask(n):
+    from . import device as dev
+    t = dev.torch()
+    return t.ones(n, dtype=t.uint8, device=dev.device())
+
+
 class MaskedKronCG(object):
     """Resident CG state for (W K W + shift I) x = W b, W = diag(mask), on one
     MI355X (gg_cgm_*): the grid GP with missing observations.  x is zero at the
@@ -303,17 +340,43 @@ class MaskedKronCG(object):
     precond='kron': z = W Q diag(1 / (lam + shift)) Q^T r from the per-factor
     eigenpairs K.schur() -- the exact inverse on the full grid, two more Kron
     matvecs per iteration (fewer iterations at low missing fractions).
+
+    noise (N positive doubles, numpy or device; a contiguous float64 device
+    tensor is used where it lies): per-point noise variances, the system (W K W
+    + D) x = W b with D = diag(noise) (gg_cgm_set_noise) -- x solves (K_oo +
+    D_oo) x_o = b_o.  noise at the missing points is ignored (NaN allowed);
+    mask=None then means every point observed.  The diagonal has one source of
+    truth: shift must be 0 or None with noise= (ValueError otherwise).
+    precond_shift (noise= only; a positive number): the scalar stand-in for
+    the noise in the 'kron' preconditioner, 1 / (lam + precond_shift) -- it is
+    no part of the system.  None takes the geometric mean of noise over the
+    observed points, a heuristic whose effect on the iteration count has not
+    been measured.  self.shift holds the stand-in (it is what gg_cgm_create
+    is given).
     """
 
-    def __init__(self, K, shift, mask, precond=None):
+    def __init__(self, K, shift, mask, precond=None, noise=None, precond_shift=None):
         from . import device as dev
         from . import native
         if precond not in (None, 'kron'):
             raise ValueError("precond must be None or 'kron'")
         self.K = K
-        self.shift = float(shift)
         self.n = int(K.shape[0])
+        if noise is not None and mask is None:
+            mask = _all_ones_mask(self.n)
         self.mask, self.n_observed = _mask_to_device(mask, self.n)
+        self.noise = None
+        if noise is not None:
+            if shift is not None and float(shift) != 0.0:
+                raise ValueError("noise= is the whole diagonal: shift must be 0 (or None); the "
+                                 "preconditioner's stand-in is precond_shift=")
+            self.noise, gmean = _noise_to_device(noise, self.n, self.mask)
+            shift = gmean if precond_shift is None else float(precond_shift)
+            if not shift > 0.0:
+                raise ValueError("precond_shift must be positive")
+        elif precond_shift is not None:
+            raise ValueError("precond_shift= needs noise=")
+        self.shift = float(shift)
         self._dk = K._device()
         L = native.lib()
         we = ctypes.c_int64()
@@ -324,6 +387,8 @@ class MaskedKronCG(object):
                                      ctypes.c_void_p(self.mask.data_ptr()),
                                      native.dptr(self.work), ctypes.byref(h)), "gg_cgm_create")
         self.h = h
+        if self.noise is not None:
+            native.check(L.gg_cgm_set_noise(h, native.dptr(self.noise)), "gg_cgm_set_noise")
         self.precond = precond
         if precond == 'kron':
             Q, T = K.schur()
@@ -381,7 +446,7 @@ class MaskedKronCG(object):
 
 def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, callback=None,
        recurrence=None, fusion=None, basis=None, comm=None, decomposition="auto",
-       mask=None, precond=None):
+       mask=None, precond=None, noise=None):
     """Solve (K + shift I) x = b with CG on the device (x0 = 0).
 
     Same stopping rule and iterates as scipy.sparse.linalg.cg (recurrence:
@@ -406,22 +471,34 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
     basis, textbook recurrence, one GPU: mask cannot be combined with comm=,
     basis='block' or an explicit recurrence='fused'.  precond='kron' (needs
     mask): the Kronecker eigenpair preconditioner of MaskedKronCG.
+
+    noise (N positive doubles, numpy or device): per-point noise variances --
+    CG on (W K W + D) x = W b, D = diag(noise) (MaskedKronCG(noise=); without
+    mask= every point is observed): x is (K_oo + D_oo)^-1 b_o on the observed
+    points; noise at the missing ones is ignored (NaN allowed).  The diagonal
+    has one source of truth: shift must be 0 (or omitted) with noise=.  The
+    rules of mask= hold (no comm=, basis='block', recurrence='fused' or
+    fusion); precond='kron' is allowed.
     """
     from . import device as dev
     n = int(K.shape[0])
-    if precond is not None and mask is None:
+    if precond is not None and mask is None and noise is None:
         raise ValueError("precond= needs mask= (on a complete grid solve_schur is exact)")
-    if mask is not None:
+    if noise is not None and shift is not None and float(shift) != 0.0:
+        raise ValueError("noise= is the whole diagonal: shift must be 0 (or omitted)")
+    if mask is not None or noise is not None:
+        what = "mask=" if mask is not None else "noise="
         if comm is not None:
-            raise ValueError("mask=: the masked CG runs on one GPU, comm= cannot be combined")
+            raise ValueError("%s: the masked CG runs on one GPU, comm= cannot be combined"
+                             % what)
         if basis == "block":
-            raise ValueError("mask=: W is not diagonal in the parity-block basis; use "
-                             "basis='grid' (or None)")
+            raise ValueError("%s: W is not diagonal in the parity-block basis; use "
+                             "basis='grid' (or None)" % what)
         if recurrence not in (None, "textbook"):
-            raise ValueError("mask=: the masked CG runs the textbook recurrence; "
-                             "recurrence='fused' cannot be combined")
+            raise ValueError("%s: the masked CG runs the textbook recurrence; "
+                             "recurrence='fused' cannot be combined" % what)
         if fusion is not None:
-            raise ValueError("mask=: the masked CG has no fusion layouts")
+            raise ValueError("%s: the masked CG has no fusion layouts" % what)
         if precond not in (None, 'kron'):
             raise ValueError("precond must be None or 'kron'")
     was_dev = dev.is_device_array(b)
@@ -432,7 +509,7 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
         maxiter = n * 10
     if check_every is None:
         check_every = 10 if n >= 1 << 20 else 50
-    if recurrence is None and mask is None:
+    if recurrence is None and mask is None and noise is None:
         recurrence = "fused"
     if comm is not None:
         from . import distributed
@@ -453,8 +530,8 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
         cg.last = CGResult(out, info, it, res, tol)
         cg.last.decomposition = how
         return out, info
-    if mask is not None:
-        solver = MaskedKronCG(K, shift, mask, precond=precond)
+    if mask is not None or noise is not None:
+        solver = MaskedKronCG(K, shift, mask, precond=precond, noise=noise)
         solver.start(bd, rtol, atol)
         solver.iterate(maxiter, check_every=check_every)
         it, conv, res, tol = solver.status()
@@ -499,7 +576,8 @@ def lanczos_info(K):
     return bool(b.value), L.value
 
 
-def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False, mask=None):
+def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False, mask=None,
+                    noise=None):
     """Device Lanczos on (K + shift I) from a Rademacher probe: (alphas, betas).
 
     work: optional device workspace of >= 4 N elements (allocated here
@@ -515,16 +593,33 @@ def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False, ma
     missing points and normalised by the observed count
     (gg_lanczos_probe_masked) -- the tridiagonal of (K_oo + shift I).  The
     count the library made is left in lanczos_tridiag.n_observed; timed=True
-    returns (alphas, betas, step_ms)."""
+    returns (alphas, betas, step_ms).
+
+    noise (N positive doubles, numpy or device; a contiguous float64 device
+    tensor is used where it lies and, like a device mask, is not checked
+    again): Lanczos on (W K W + D), D = diag(noise), the tridiagonal of K_oo +
+    D_oo (gg_lanczos_probe_masked_noise; without mask= every point is
+    observed).  shift must be 0 and timed=True is not offered."""
     from . import device as dev
     from . import native
     dk = K._device()
     n = int(K.shape[0])
+    if noise is not None:
+        if shift is not None and float(shift) != 0.0:
+            raise ValueError("noise= is the whole diagonal: shift must be 0")
+        shift = 0.0
+        if timed:
+            raise ValueError("noise=: the probe has no timed twin")
+        if mask is None:
+            mask = _all_ones_mask(n)
     if mask is not None:
         steps = int(steps)
         if steps < 1:
             raise ValueError("Lanczos needs steps >= 1")
         md = _mask_device_bytes(mask, n)
+    if noise is not None:
+        # a device vector is taken as it is, like a device mask
+        nd = _noise_to_device(noise, n, md, check=not _is_device_doubles(noise))[0]
     if work is None:
         work = dev.empty(4 * n)
     elif int(work.numel()) < 4 * n:
@@ -536,7 +631,11 @@ def lanczos_tridiag(K, shift, steps, seed=0, probe=0, work=None, timed=False, ma
         nobs = ctypes.c_int64()
         args = (dk.h, float(shift), ctypes.c_void_p(md.data_ptr()), int(seed), int(probe), steps,
                 native.dptr(work), a, b, ctypes.byref(done), ctypes.byref(nobs))
-        if timed:
+        if noise is not None:
+            native.check(native.lib().gg_lanczos_probe_masked_noise(
+                dk.h, native.dptr(nd), *(args[2:] + (native.stream_ptr(),))),
+                "gg_lanczos_probe_masked_noise")
+        elif timed:
             sm = (ctypes.c_double * steps)()
             native.check(native.lib().gg_lanczos_probe_masked_timed(
                 *(args + (sm, native.stream_ptr()))), "gg_lanczos_probe_masked_timed")
@@ -587,21 +686,28 @@ def _mask_device_bytes(mask, n):
     return _mask_to_device(mask, n)[0]
 
 
-def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None):
+def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None, noise=None):
     """Stochastic Lanczos quadrature estimate of log det(K + shift I):
     (mean, per-probe estimates).
 
     mask (as lanczos_tridiag): the estimate of log det(K_oo + shift I) on the
     observed points -- each probe's quadrature is scaled by the observed count
     and steps is capped at it; its cost is probes x steps Kronecker matvecs
-    whatever the number of missing points."""
+    whatever the number of missing points.
+
+    noise (as lanczos_tridiag; checked once here): the estimate of
+    log det(K_oo + D_oo), D = diag(noise); shift must be 0."""
     n = int(K.shape[0])
     scale, kw = n, {}
+    if noise is not None and mask is None:
+        mask = _all_ones_mask(n)
     if mask is not None:
         from . import device as dev
         md, scale = _mask_to_device(mask, n)
         steps = min(int(steps), scale)
         kw = dict(work=dev.empty(4 * n), mask=md)
+        if noise is not None:
+            kw["noise"] = _noise_to_device(noise, n, md)[0]
     ests = []
     for j in range(probes):
         a, b = lanczos_tridiag(K, shift, steps, seed=seed, probe=j, **kw)
@@ -611,7 +717,8 @@ def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None):
     return float(np.mean(ests)), np.array(ests)
 
 
-def trace_grad(K, dKs, shift, mask=None, probes=8, seed=0, rtol=1e-10, Z=None, solver=None):
+def trace_grad(K, dKs, shift, mask=None, probes=8, seed=0, rtol=1e-10, Z=None, solver=None,
+               noise=None, noise_scale=None):
     """Probe estimates of the traces in the marginal likelihood's gradient:
     (means, per_probe) with A = W K W + shift I, W = diag(mask) (the identity
     without a mask).  per_probe is probes x (1 + len(dKs)): column 0 is
@@ -628,13 +735,35 @@ def trace_grad(K, dKs, shift, mask=None, probes=8, seed=0, rtol=1e-10, Z=None, s
     MaskedKronCG (KronCG without a mask) to rtol plus len(dKs) Kronecker
     matvecs and dots; the vectors are reused across probes.  solver: a resident
     MaskedKronCG / KronCG of (K, shift, mask) to solve with instead of a new
-    one (GPGridModel passes its own, with its preconditioner)."""
+    one (GPGridModel passes its own, with its preconditioner).
+
+    noise, noise_scale (given together; N doubles each, numpy or device): the
+    per-point noise noise = noise_var * noise_scale, A = W K W + diag(noise)
+    (MaskedKronCG(noise=); shift must then be 0).
+    Column 0 becomes (A^-1 z)^T (noise_scale o z), the estimate of tr(A_oo^-1
+    diag(noise_scale)_oo): the trace in the derivative by noise_var.  With
+    solver= the solver's own noise is used and only noise_scale is needed."""
     from . import dense
     from . import device as dev
     from . import native
     n = int(K.shape[0])
     t = dev.torch()
     wd = None
+    if noise is None and solver is not None:
+        noise = getattr(solver, "noise", None)
+    if (noise is None) != (noise_scale is None):
+        raise ValueError("noise= and noise_scale= are given together")
+    if noise is not None and solver is None:
+        if shift is not None and float(shift) != 0.0:
+            raise ValueError("noise= is the whole diagonal: shift must be 0")
+        solver = MaskedKronCG(K, None, mask, noise=noise)
+    if noise is not None:
+        mask = solver.mask
+        nsd = dev.to_device(noise_scale)
+        if nsd.numel() != n:
+            raise ValueError("noise_scale must have %d entries" % n)
+        # a select: noise_scale at a missing point may be NaN
+        nsd = t.where(solver.mask != 0, nsd, t.zeros_like(nsd))
     if mask is not None:
         if solver is None:
             solver = MaskedKronCG(K, shift, mask)
@@ -664,7 +793,11 @@ def trace_grad(K, dKs, shift, mask=None, probes=8, seed=0, rtol=1e-10, Z=None, s
         it, conv = solver.status()[:2]
         if not conv:
             logger.info('trace_grad: probe %d did not converge in %d iterations' % (j, it))
-        per[j, 0] = dense.dot(z, x)
+        if noise is not None:
+            t.mul(z, nsd, out=w)
+            per[j, 0] = dense.dot(x, w)
+        else:
+            per[j, 0] = dense.dot(z, x)
         for k, dK in enumerate(dKs):
             dK.matvec_device(z, out=w)
             per[j, 1 + k] = dense.dot(x, w)
@@ -697,27 +830,41 @@ class GridPosteriorSampler(object):
     allowed).  rtol: the CG's relative tolerance.  schur: (Q, T) of K.schur()
     to reuse.  The work vectors (three of N doubles, two in the eigenbasis
     route besides Q^T y) are held across draws.
+
+    noise (N positive doubles, numpy or device): per-point noise variances, y =
+    f + e with e_i ~ N(0, noise_i) at the observed points.  Matheron's route
+    only (solver='exact' raises): b = y - f - sqrt(noise) o e
+    (gg_sample_residual_noise) and alpha from MaskedKronCG(noise=); without
+    mask= every point is observed.  shift must then be 0 or None; a masked_cg
+    given must carry the noise itself.
     """
 
     MAX_DRAWS = 32768
 
     def __init__(self, K, shift, y_dev, mask=None, solver=None, precond=None, rtol=1e-10,
-                 seed=0, masked_cg=None, schur=None):
+                 seed=0, masked_cg=None, schur=None, noise=None):
         from . import device as dev
         from . import native
+        if noise is None and masked_cg is not None:
+            noise = getattr(masked_cg, "noise", None)
         if solver is None:
-            solver = 'exact' if mask is None and masked_cg is None else 'cg'
+            solver = 'exact' if mask is None and masked_cg is None and noise is None else 'cg'
         if solver not in ('exact', 'cg'):
             raise ValueError("solver must be 'exact' or 'cg'")
-        masked = mask is not None or masked_cg is not None
+        if noise is not None and solver == 'exact':
+            raise ValueError("noise=: the eigenbasis does not diagonalise K + diag(noise); "
+                             "use solver='cg' (Matheron's rule)")
+        masked = mask is not None or masked_cg is not None or noise is not None
         if masked and solver == 'exact':
             raise ValueError("mask=: solver='exact' does not apply to an incomplete grid; "
                              "use solver='cg'")
         if precond is not None and not masked:
             raise ValueError("precond= needs mask=")
         self.K = K
-        self.shift = float(shift)
-        if not self.shift > 0.0:
+        self.shift = 0.0 if shift is None else float(shift)
+        if noise is not None and masked_cg is None and self.shift != 0.0:
+            raise ValueError("noise= is the whole diagonal: shift must be 0 (or None)")
+        if noise is None and not self.shift > 0.0:
             raise ValueError("shift (the noise variance) must be positive")
         self.n = int(K.shape[0])
         self.rtol = float(rtol)
@@ -730,14 +877,21 @@ class GridPosteriorSampler(object):
         self._d = len(lam)
         self._ms = native.i64_array([l.size for l in lam])
         self._lam = dev.to_device(np.concatenate(lam))
-        self.mask = self._cg = None
+        self.mask = self._cg = self.noise = None
         if masked:
             self.route = 'matheron'
             self._cg = masked_cg if masked_cg is not None else \
-                MaskedKronCG(K, self.shift, mask, precond=precond)
-            if self._cg.n != self.n or self._cg.shift != self.shift:
+                (MaskedKronCG(K, self.shift, mask, precond=precond) if noise is None else
+                 MaskedKronCG(K, None, mask, precond=precond, noise=noise))
+            if noise is not None:
+                if self._cg.n != self.n or self._cg.noise is None:
+                    raise ValueError("masked_cg solves another system")
+                self.shift = self._cg.shift
+            elif self._cg.n != self.n or self._cg.shift != self.shift or \
+                    getattr(self._cg, "noise", None) is not None:
                 raise ValueError("masked_cg solves another system")
             self.mask = self._cg.mask
+            self.noise = self._cg.noise
         elif solver == 'cg':
             self.route = 'matheron'
             self._cg = KronCG(K, self.shift)
@@ -772,9 +926,14 @@ class GridPosteriorSampler(object):
             sp()), "gg_kron_prior_coeffs")
         self.Q.matvec_device(self._c, out=self._f)
         mp = None if self.mask is None else ctypes.c_void_p(self.mask.data_ptr())
-        native.check(L.gg_sample_residual(
-            native.dptr(self.y), native.dptr(self._f), mp, float(np.sqrt(self.shift)),
-            self.seed, s1, native.dptr(self._c), self.n, sp()), "gg_sample_residual")
+        if self.noise is not None:
+            native.check(L.gg_sample_residual_noise(
+                native.dptr(self.y), native.dptr(self._f), native.dptr(self.noise), mp,
+                self.seed, s1, native.dptr(self._c), self.n, sp()), "gg_sample_residual_noise")
+        else:
+            native.check(L.gg_sample_residual(
+                native.dptr(self.y), native.dptr(self._f), mp, float(np.sqrt(self.shift)),
+                self.seed, s1, native.dptr(self._c), self.n, sp()), "gg_sample_residual")
         cg_ = self._cg
         cg_.start(self._c, self.rtol, 0.0, x_out=self._alpha)
         cg_.iterate(self.n * 10, check_every=10 if self.n >= 1 << 20 else 50)

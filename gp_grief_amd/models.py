@@ -718,12 +718,33 @@ class GPGridModel(BaseModel):
     ones included) and their streamed mean / variance -- one Kronecker matvec
     per draw with solver='exact', one (masked) CG solve per draw otherwise
     (linalg.GridPosteriorSampler).
+
+    noise_scale (N positive doubles, numpy or device; fixed): per-point noise,
+    the variance of observation i is noise_var * noise_scale[i] -- a pixel
+    averaged from c readings has noise_scale 1 / c, a product with an error
+    map ships it.  noise_var stays the one scalar hyperparameter.  With or
+    without mask= (values at the missing points are ignored, NaN allowed).  The
+    system is W K W + D, D = diag(noise_var * noise_scale), which no
+    eigendecomposition diagonalises: the solver is the weighted masked CG
+    (solver='cg', the default here; 'exact' raises), logdet must be 'lanczos'
+    (weighted SLQ, an estimator of log det(K_oo + D_oo)), and the LML is
+    -1/2 (y_o^T alpha + log det(K_oo + D_oo) + n log 2 pi).  The adjoint
+    gradient's noise entry is 1/2 alpha^T (noise_scale o alpha) - 1/2 tr(A^-1
+    diag(noise_scale)), the trace by probes.  precond='kron' uses 1 / (lam +
+    noise_var * g), g the geometric mean of noise_scale over the observed
+    points: a heuristic stand-in, its effect on the iteration count unmeasured.
+    predict(Xnew) solves with the weighted system and adds the scalar noise_var
+    to the variance: the noise of a new observation is the caller's choice
+    (subtract noise_var for the latent variance, add your own).
+    predict_grid(compute_var=True) raises as with a mask (posterior_moments
+    gives sampled variances); sample_posterior / posterior_moments draw by
+    Matheron's rule with e_i ~ N(0, noise_var * noise_scale[i]).
     """
 
     def __init__(self, xg, Y, kern, noise_var=1., solver=None, logdet='exact',
                  dim_noise_var=1e-12, cg_rtol=1e-10, slq_probes=8, slq_steps=50, seed=0,
                  mask=None, precond=None, exact_missing_max=1024,
-                 grad_method='finite_difference', grad_probes=None):
+                 grad_method='finite_difference', grad_probes=None, noise_scale=None):
         super(GPGridModel, self).__init__()
         from .kern import GridKernel
         assert isinstance(kern, GridKernel)
@@ -736,10 +757,20 @@ class GPGridModel(BaseModel):
                 raise ValueError("grad_method='adjoint' needs a GridKernel of plain stationary "
                                  "1-D kernels (%s); use grad_method='finite_difference'" % e)
         if solver is None:
-            solver = 'exact' if mask is None else 'cg'
+            solver = 'exact' if mask is None and noise_scale is None else 'cg'
         if solver not in ('exact', 'cg'):
             raise ValueError("solver must be 'exact' or 'cg'")
-        if mask is None:
+        if noise_scale is not None:
+            if solver == 'exact':
+                raise ValueError("noise_scale=: solver='exact' does not apply (no "
+                                 "eigendecomposition diagonalises K + diag(noise)); use "
+                                 "solver='cg'")
+            if logdet != 'lanczos':
+                raise ValueError("noise_scale=: logdet must be 'lanczos' (the weighted "
+                                 "stochastic Lanczos quadrature), not %r" % (logdet,))
+            if precond not in (None, 'kron'):
+                raise ValueError("precond must be None or 'kron'")
+        elif mask is None:
             if logdet == 'lanczos':
                 raise ValueError("logdet='lanczos' is the masked estimator and needs mask=; "
                                  "a complete grid uses logdet='slq'")
@@ -773,13 +804,23 @@ class GPGridModel(BaseModel):
         self.precond = precond
         self.exact_missing_max = int(exact_missing_max)
         self._mask = self._mcg = self._mcg_key = None
+        self._nscale = self._nscale_gmean = None
         self.num_observed = self.num_data
+        if noise_scale is not None and mask is None:
+            from .linalg import _all_ones_mask
+            mask = _all_ones_mask(self.num_data)
         if mask is not None:
             from .linalg import _mask_to_device
             self._mask, self.num_observed = _mask_to_device(mask, self.num_data)
             # Y at the missing points is never read again (it may be NaN)
             t = dev.torch()
             self._yd = t.where(self._mask != 0, self._yd, t.zeros_like(self._yd))
+        if noise_scale is not None:
+            from .linalg import _noise_to_device
+            t = dev.torch()
+            ns, self._nscale_gmean = _noise_to_device(noise_scale, self.num_data, self._mask)
+            # a copy with 1 at the missing points (a select: NaN allowed there)
+            self._nscale = t.where(self._mask != 0, ns, t.ones_like(ns))
         self.grad_method = grad_method
         self.grad_probes = int(slq_probes if grad_probes is None else grad_probes)
         self.grad_estimates = None
@@ -809,7 +850,13 @@ class GPGridModel(BaseModel):
         K = self._operator()
         key = (id(K), float(self.noise_var))
         if self._mcg is None or self._mcg_key != key:
-            self._mcg = MaskedKronCG(K, float(self.noise_var), self._mask, precond=self.precond)
+            s = float(self.noise_var)
+            if self._nscale is None:
+                self._mcg = MaskedKronCG(K, s, self._mask, precond=self.precond)
+            else:
+                self._mcg = MaskedKronCG(K, None, self._mask, precond=self.precond,
+                                         noise=s * self._nscale,
+                                         precond_shift=s * self._nscale_gmean)
             self._mcg_key = key
         return self._mcg
 
@@ -909,6 +956,11 @@ class GPGridModel(BaseModel):
         is fixed, so the objective is deterministic."""
         from .linalg import slq_logdet
         probes, steps, seed = self.slq
+        if self._nscale is not None:
+            mean, self.slq_estimates = slq_logdet(
+                self._operator(), 0.0, probes=probes, steps=steps, seed=seed, mask=self._mask,
+                noise=float(self.noise_var) * self._nscale)
+            return mean
         mean, self.slq_estimates = slq_logdet(self._operator(), float(self.noise_var),
                                               probes=probes, steps=steps, seed=seed,
                                               mask=self._mask)
@@ -980,8 +1032,12 @@ class GPGridModel(BaseModel):
         ops = [replaced(*grads[k]) for k in idx]
         alpha = self._alpha
         fit_terms = np.zeros(parameters.shape)
-        fit_terms[0] = 0.5 * dense.dot(alpha, alpha)
         w = dev.empty(self.num_data)
+        if self._nscale is None:
+            fit_terms[0] = 0.5 * dense.dot(alpha, alpha)
+        else:
+            dev.torch().mul(alpha, self._nscale, out=w)
+            fit_terms[0] = 0.5 * dense.dot(alpha, w)
         for k, op in zip(idx, ops):
             op.matvec_device(alpha, out=w)
             fit_terms[1 + k] = 0.5 * dense.dot(alpha, w)
@@ -990,7 +1046,8 @@ class GPGridModel(BaseModel):
             means, self.grad_estimates = trace_grad(K, ops, s, mask=self._mask,
                                                     probes=self.grad_probes, seed=self.slq[2],
                                                     rtol=self.cg_rtol,
-                                                    solver=self._masked_cg())
+                                                    solver=self._masked_cg(),
+                                                    noise_scale=self._nscale)
             traces[:] = means
         else:
             Q, T = self._schur()
@@ -1024,6 +1081,11 @@ class GPGridModel(BaseModel):
         eigenpairs, streamed on the device)."""
         from . import native
         from .tensors import KronMatrix
+        if self._nscale is not None and compute_var:
+            raise ValueError("noise_scale=: the grid posterior variance is not available with "
+                             "per-point noise; call predict_grid(compute_var=False) for the "
+                             "mean K alpha, posterior_moments(n_samples) for sampled "
+                             "variances, or predict(Xnew) for point variances")
         if self._mask is not None and compute_var:
             raise ValueError("mask=: the grid posterior variance is not available on an "
                              "incomplete grid; call predict_grid(compute_var=False) for the "

@@ -111,6 +111,7 @@ SIGNATURES = {
     "gg_cgm_create": [_vp, ctypes.c_double, _vp, _c_dp, ctypes.POINTER(ctypes.c_void_p)],
     "gg_cgm_destroy": [_vp],
     "gg_cgm_set_precond": [_vp, _vp, _c_dp],
+    "gg_cgm_set_noise": [_vp, _c_dp],
     "gg_cgm_start": [_vp, _c_dp, _c_dp, ctypes.c_double, ctypes.c_double, _vp],
     "gg_cgm_iterate": [_vp, ctypes.c_int, ctypes.c_int, _vp],
     "gg_cgm_status": [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
@@ -133,6 +134,10 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_int), _c_i64p,
                                       ctypes.POINTER(ctypes.c_double), _vp],
+    "gg_lanczos_probe_masked_noise": [_vp, _c_dp, _vp, ctypes.c_uint64, ctypes.c_int,
+                                      ctypes.c_int, _c_dp, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_int), _c_i64p, _vp],
     "gg_probe_fill": [ctypes.c_uint64, ctypes.c_int, _c_dp, ctypes.c_int64, _vp],
     "gg_normal_fill": [ctypes.c_uint64, ctypes.c_int, _c_dp, ctypes.c_int64, _vp],
     "gg_kron_posterior_coeffs": [ctypes.c_int, _c_i64p, _c_dp, ctypes.c_double, _c_dp,
@@ -141,6 +146,8 @@ SIGNATURES = {
                              _vp],
     "gg_sample_residual": [_c_dp, _c_dp, _vp, ctypes.c_double, ctypes.c_uint64, ctypes.c_int,
                            _c_dp, ctypes.c_int64, _vp],
+    "gg_sample_residual_noise": [_c_dp, _c_dp, _c_dp, _vp, ctypes.c_uint64, ctypes.c_int, _c_dp,
+                                 ctypes.c_int64, _vp],
     "gg_sample_accumulate": [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int64,
                              _vp],
     "gg_sym_eig_batched": [ctypes.c_int, _c_i64p, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64,

@@ -392,6 +392,23 @@ int gg_cgm_destroy(gg_cgm* cgm);
  * Two more Kronecker matvecs, a decoded divide and a dot per iteration; the
  * handle allocates its two extra vectors.  The stopping test stays on |r|.   */
 int gg_cgm_set_precond(gg_cgm* cgm, const gg_kron* Q, const double* lam_dev);
+/* Optional per-point noise (before gg_cgm_start; noise_dev == NULL: off again):
+ * A = W K W + D, D = diag(noise), the grid GP whose observations have unequal
+ * variances (and the operator of a Laplace approximation's Newton step).
+ * noise_dev: n doubles on the device at any 8-byte aligned address; the
+ * handle keeps the pointer.  The 16-byte-lane kernels run only where every
+ * stream of a pass allows them: the direction pass needs noise_dev 16-byte
+ * aligned, the update pass noise_dev and x_dev both; one of them off by 8
+ * bytes puts the whole pass on 8-byte lanes.  Precondition: noise > 0
+ * at every observed point (not checked here); at the missing points it is
+ * never used -- a select, it may be NaN.  The matvec then runs with shift 0
+ * (its epilogue yields p.K p), the direction pass adds sum_i noise_i p_i^2 and
+ * the update pass uses select(mask, t_i + noise_i p_i, 0): two more reads of n
+ * doubles per iteration, no more launches.  The `shift` given at create then
+ * only feeds the preconditioner, 1 / (lam + shift): any positive
+ * representative of the noise will do.  GG_ERR_VALUE, the handle unchanged:
+ * a NULL handle, a call after gg_cgm_start, a misaligned noise_dev.         */
+int gg_cgm_set_noise(gg_cgm* cgm, const double* noise_dev);
 /* r = select(mask, b, 0), x = 0, tolerance max(atol, rtol |W b|).  b_dev and
  * x_dev at any 8-byte aligned address (16-byte: the double2 kernels).       */
 int gg_cgm_start(gg_cgm* cgm, const double* b_dev, double* x_dev, double rtol, double atol,
@@ -479,6 +496,26 @@ int gg_lanczos_probe_masked_timed(const gg_kron* K, double shift, const uint8_t*
                                   double* alphas_host, double* betas_host, int* steps_done,
                                   int64_t* n_observed, double* step_ms_host,
                                   gg_stream stream);
+/* The masked probe with per-point noise: Lanczos on A = W K W + D, D =
+ * diag(noise), from the same start vector -- the tridiagonal of K_oo + D_oo,
+ * the quadrature behind log det(K_oo + D_oo).  noise_dev: n doubles on the
+ * device, 8-byte aligned (16-byte: the double2 kernels); precondition noise >
+ * 0 at every observed point (not checked here), never used at the missing
+ * ones (a select: NaN allowed).  The matvec runs with shift 0; the pass that
+ * makes a vector u (the start pass, then each update pass) also sums
+ * noise_i u_i^2 for the next alpha, and the update is w = select(mask,
+ * cy (Y + noise o u), 0) + cu u + cp u_prev: one more read of n doubles per
+ * step.  The 16-byte lanes of a pass also need noise_dev 16-byte aligned.
+ * Everything else as gg_lanczos_probe_masked (one driver runs both).
+ * GG_ERR_VALUE, the host outputs untouched: a NULL K, noise_dev, mask_dev,
+ * work_dev, alphas_host or betas_host, a misaligned noise_dev, a non-square
+ * operator or factors, steps < 1 (all before any launch); or a mask with no
+ * observed point (found after the run: *n_observed = 0 is written, the
+ * arrays and *steps_done are not).                                           */
+int gg_lanczos_probe_masked_noise(const gg_kron* K, const double* noise_dev,
+                                  const uint8_t* mask_dev, uint64_t seed, int probe, int steps,
+                                  double* work_dev, double* alphas_host, double* betas_host,
+                                  int* steps_done, int64_t* n_observed, gg_stream stream);
 int gg_probe_fill(uint64_t seed, int probe, double* z_dev, int64_t n, gg_stream stream);
 
 /* ------------------------------------ posterior sampling
@@ -525,6 +562,14 @@ int gg_kron_prior_coeffs(int d, const int64_t* m, const double* lam_dev, uint64_
 int gg_sample_residual(const double* y_dev, const double* f_dev, const uint8_t* mask_dev,
                        double noise_sd, uint64_t seed, int stream, double* b_dev, int64_t n,
                        gg_stream s);
+/* The same with per-point noise: b[i] = y[i] - f[i] - sqrt(noise[i]) z[i] where
+ * observed, exactly 0 elsewhere (noise at a missing point is selected away
+ * with y: NaN allowed).  noise_dev: n doubles, 8-byte aligned, >= 0 at the
+ * observed points (precondition).  mask_dev may be NULL.  Refusals as
+ * gg_sample_residual, and a NULL noise_dev.                                  */
+int gg_sample_residual_noise(const double* y_dev, const double* f_dev, const double* noise_dev,
+                             const uint8_t* mask_dev, uint64_t seed, int stream, double* b_dev,
+                             int64_t n, gg_stream s);
 /* x = f + w (Matheron: the prior draw plus K alpha), stored to out_dev (may be
  * NULL, or f_dev / w_dev themselves) and folded into Welford's running moments
  * as draw number k = 1, 2, .. (mean_dev, m2_dev: both given or both NULL;
