@@ -58,6 +58,7 @@ typedef double bd4 __attribute__((ext_vector_type(4)));
 constexpr int kBlkMaxD = 6;        // 2^d corner values per fold thread
 constexpr int kBlkModeWaves = 12;  // waves per blk_mode_kernel workgroup (3 / SIMD)
 constexpr int kBlkPairWaves = 4;   // waves per blk_pair_kernel workgroup (2 slabs)
+constexpr int kBlkModeStripsDefault = 3;   // GG_BLK_MODE_STRIPS when unset
 
 struct BlockOp {
   int d = 0;
@@ -83,6 +84,13 @@ struct BlockOp {
   bool pair_lds = false;
   int pair_spw = 1;
   bool fast = true;   // blk_mode_fast_kernel where instantiated (GG_BLK_MODE_FAST=0: off)
+  // blk_mode_fast_kernel with two strips per wave (GG_BLK_MODE_STRIPS, a mask:
+  // bit 0 the plain launches, bit 1 the CG prologues; 0: one strip per wave
+  // everywhere.  The Lanczos prologue stays at one strip: its two-strip form
+  // was faster in five of six interleaved pairs, 0.2-0.4 ms of 11.6 in the
+  // mean, but on boxes whose spread on that launch was larger (0.5-1.1 ms,
+  // profiles/r08), and was removed again)
+  int strips = kBlkModeStripsDefault;
   // the CG prologue's r / q_old / p_old loads and r / p_new stores non-temporal
   // (default; GG_BLK_PRO_NT=0 off): 200^4 prologue 13.84-14.02 -> 13.52-13.58
   // ms, interleaved processes (profiles/r05/y_pro_nt)
@@ -260,6 +268,27 @@ __device__ __forceinline__ void stuq(void* p, int64_t uoff, uint32_t voff, doubl
 // 16-byte global accesses (per-lane addresses)
 typedef double gd2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) gd2v gd2;
+// 16 bytes per lane in the uniform base + lane offset form of ldu / lduq
+template <bool NT>
+__device__ __forceinline__ gd2v lduq2(const void* p, int64_t uoff, uint32_t voff) {
+  gchar* b = reinterpret_cast<gchar*>(reinterpret_cast<uintptr_t>(ubase(p, uoff)));
+  if constexpr (!NT) return *reinterpret_cast<const gd2*>(b + voff);
+  return __builtin_nontemporal_load(reinterpret_cast<const gd2*>(b + voff));
+}
+// the 16-byte store of a two-strip window: lanes with `own` to base + lane
+// offset, the others (a spare window, the lanes of a half window past the row)
+// to their trash slot `tp` -- a per-lane 64-bit address, one store instruction
+// whatever the mask (the wait counts stay fixed)
+template <bool NT>
+__device__ __forceinline__ void stw2(bool own, void* p, int64_t uoff, uint32_t voff, gchar* tp,
+                                     gd2v v) {
+  gchar* b = reinterpret_cast<gchar*>(reinterpret_cast<uintptr_t>(ubase(p, uoff)));
+  gd2* q = reinterpret_cast<gd2*>(own ? b + voff : tp);
+  if constexpr (!NT)
+    *q = v;
+  else
+    __builtin_nontemporal_store(v, q);
+}
 __device__ __forceinline__ double2 ld2g(const double* p) {
   const gd2v v = *reinterpret_cast<const gd2*>(reinterpret_cast<uintptr_t>(p));
   return double2{v.x, v.y};
@@ -643,17 +672,35 @@ __device__ __attribute__((aligned(16))) double g_blk_trash[6 * 64];
 // launch, 8 (2 per SIMD, 256 registers) for the fused ones
 // (KIND 3: the prologue, KIND 1, with its r / q_old / p_old loads and r /
 // p_new stores non-temporal -- Y, read by the next launch, stays normal)
-template <int KIND>
+//
+// SW = 2 (GG_BLK_MODE_STRIPS): a wave owns a window of two adjacent strips, 32
+// columns of one outer index.  Lane n16 holds columns 2 n16 and 2 n16 + 1, so
+// every global access is 16 bytes per lane (256-B row segments per wave) and
+// each fragment read feeds two MFMAs, the even columns' and the odd columns',
+// into two accumulator sets.  An MFMA's column n depends on the B operand's
+// column n alone, and each output element takes its k-steps in the order and
+// from the fragments of SW = 1: Y is bitwise the same.  A row with an odd strip
+// count ends in a half window: its lanes n16 >= 8 load the window's valid half
+// again, add nothing to the partials and store to their trash slot.  `spb`,
+// `gpb` and the cursors count windows.
+// The plain kind with two strips: eight waves (2 per SIMD) with the whole
+// strip in flight, 230 VGPRs at TF 6.  (Twelve waves with a 5-deep ring, 159
+// VGPRs, measured level with it: 5.71-5.75 against 5.71-5.78 ms at 200^4,
+// profiles/r08.)
+template <int KIND, int SW = 1>
 constexpr int fast_waves() {
-  return KIND == 0 ? 12 : 8;
+  return (KIND == 0 && SW == 1) ? 12 : 8;
 }
 
-template <int TF, int KIND_>
-__global__ __launch_bounds__(64 * fast_waves<KIND_>(), 1) void blk_mode_fast_kernel(ModeArgs a) {
+template <int TF, int KIND_, int SW = 1>
+__global__ __launch_bounds__((64 * fast_waves<KIND_, SW>()), 1) void blk_mode_fast_kernel(ModeArgs a) {
+  static_assert(SW == 1 || SW == 2, "one or two strips per wave");
+  static_assert(SW == 1 || (KIND_ != 2 && KIND_ != 4),
+                "the side-job and Lanczos kinds stay at one strip per wave");
   constexpr bool NT = KIND_ >= 3;   // KIND 4 (Lanczos), 5 (derived r): non-temporal too
   constexpr bool RDER = KIND_ == 5;
   constexpr int KIND = (KIND_ == 3 || KIND_ == 5) ? 1 : KIND_;
-  constexpr int W = fast_waves<KIND>();
+  constexpr int W = fast_waves<KIND, SW>();
   constexpr int JT = TF + 1;
   constexpr int KS = 4 * TF + 1;
   constexpr int kD = KIND == 0 ? KS : (KS % 5 == 0) ? 5 : (KS % 3 == 0) ? 3 : KS;   // ring depth, divides KS
@@ -665,9 +712,21 @@ __global__ __launch_bounds__(64 * fast_waves<KIND_>(), 1) void blk_mode_fast_ker
   const int n16 = lane & 15, kq = lane >> 4;
   const int64_t g0 = (int64_t)blockIdx.x * a.per_wg;
   const int64_t g1 = min(a.ngroups, g0 + a.per_wg);
-  const int64_t cpr = a.inner >> 4;
-  uint32_t o_e = (uint32_t)(((int64_t)kq * a.inner + n16) * 8);
+  // strips (SW = 2: windows) per row; an odd strip count leaves a half window
+  const int64_t cpr = ((a.inner >> 4) + (SW - 1)) / SW;
+  const bool odd = SW == 2 && ((a.inner >> 4) & 1) != 0;
+  uint32_t o_e = (uint32_t)(((int64_t)kq * a.inner + SW * n16) * 8);
   asm volatile("" : "+v"(o_e));
+  // SW = 2 only: a half window's lane offset (lanes 8..15 on the columns of
+  // lanes 0..7), whether this lane is one of the lower eight, and (below)
+  // the lane's trash slot as a full address for stw2
+  [[maybe_unused]] uint32_t o_h = 0;
+  [[maybe_unused]] bool lo8 = true;
+  if constexpr (SW == 2) {
+    o_h = (uint32_t)(((int64_t)kq * a.inner + 2 * (n16 & 7)) * 8);
+    asm volatile("" : "+v"(o_h));
+    lo8 = n16 < 8;
+  }
   const int64_t rstep = a.inner * 32;
   double* trash = g_blk_trash + 2 * lane;   // 16 bytes per lane: spare stores land here
   // a store whose wave-uniform `valid` sends it to the trash slot instead:
@@ -681,6 +740,9 @@ __global__ __launch_bounds__(64 * fast_waves<KIND_>(), 1) void blk_mode_fast_ker
     void* bp = valid ? p : static_cast<void*>(g_blk_trash);
     stuq<NT>(bp, valid ? uoff : 0, valid ? voff : o_t, v);
   };
+  [[maybe_unused]] gchar* tp2 = nullptr;
+  if constexpr (SW == 2)
+    tp2 = reinterpret_cast<gchar*>(reinterpret_cast<uintptr_t>(g_blk_trash)) + o_t;
 
   struct Cur {
     int64_t B, lg, o, cs;
@@ -715,10 +777,17 @@ __global__ __launch_bounds__(64 * fast_waves<KIND_>(), 1) void blk_mode_fast_ker
       o = (a.spb - 1) / cpr;
       cs = (a.spb - 1) - o * cpr;
     }
-    return uni64(c.B * a.nb + o * (int64_t)a.h * a.inner + (cs << 4));
+    return uni64(c.B * a.nb + o * (int64_t)a.h * a.inner + cs * (16 * SW));
   };
   auto cur_valid = [&](const Cur& c) -> bool {
     return __builtin_amdgcn_readfirstlane((int)(c.lg * W + wave < a.spb)) != 0;
+  };
+  // the row's last window when its strip count is odd (a spare window reads
+  // the block's last one: spb is a multiple of cpr, so that is a row's last)
+  auto cur_half = [&](const Cur& c) -> bool {
+    if (SW == 1) return false;
+    const bool last = c.lg * W + wave >= a.spb || c.cs == cpr - 1;
+    return __builtin_amdgcn_readfirstlane((int)(odd && last)) != 0;
   };
 
   bool first = false, pqo_on = false;
@@ -781,6 +850,111 @@ __global__ __launch_bounds__(64 * fast_waves<KIND_>(), 1) void blk_mode_fast_ker
         *reinterpret_cast<double2*>(lds + i) = *reinterpret_cast<const double2*>(src + i);
     }
     __syncthreads();
+
+    if constexpr (SW == 2) {
+      // the segment's stream as below, a window per cursor step: .x the even
+      // columns' strip, .y the odd columns'
+      Cur lc = cur_at(sg0);
+      int64_t lg_n = sg0;
+      int64_t l_base = cur_base(lc);
+      uint32_t l_oe = cur_half(lc) ? o_h : o_e;
+      gd2v ring[kD][3];
+      auto issue = [&](int slot, int s) {
+        const int64_t ub = l_base * 8 + (int64_t)s * rstep;
+        ring[slot][0] = lduq2<NT>(a.X, ub, l_oe);
+        if (KIND == 1) {
+          ring[slot][1] = lduq2<NT>(rsrc, ub, l_oe);
+          ring[slot][2] = lduq2<NT>(a.q_old, ub, l_oe);
+        }
+      };
+      auto load_next_strip = [&] {
+        if (lg_n + 1 < sg1) {
+          cur_next(lc);
+          l_base = cur_base(lc);
+          l_oe = cur_half(lc) ? o_h : o_e;
+        }
+        ++lg_n;
+      };
+#pragma unroll
+      for (int u = 0; u < kD; ++u) issue(u, u);
+
+      Cur cc = cur_at(sg0);
+#pragma unroll 1
+      for (int64_t g = sg0; g < sg1; ++g) {
+        const int64_t cbase = cur_base(cc);
+        const bool chalf = cur_half(cc);
+        const uint32_t c_oe = chalf ? o_h : o_e;
+        // this lane's columns are the window's own: not a spare window, not
+        // past the row
+        const bool own = cur_valid(cc) && (lo8 || !chalf);
+        const bool own_rr = own && pending, own_pq = own && pqo_on;
+        uint32_t lo = (uint32_t)(lane * 8);
+        asm volatile("" : "+v"(lo));
+        const char* lb = reinterpret_cast<const char*>(lds) + lo;
+        bd4 acc[2][TF];
+        double acc4[2] = {0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < TF; ++t) acc[0][t] = acc[1][t] = bd4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const int slot = s % kD;
+          gd2v xb = ring[slot][0];
+          if (KIND == 1) {
+            // per element the expressions of SW = 1
+            const gd2v q = ring[slot][2];
+            const int64_t ub = (cbase + (int64_t)4 * s * a.inner) * 8;
+            gd2v r;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              double rc = rst ? ring[slot][1][c] : fma(-bprev, ring[slot][1][c], xb[c]);
+              rc = rc - alpha * q[c];
+              const double rr = fma(rc, rc, rr_acc);
+              xb[c] = first ? rc : fma(beta, xb[c], rc);
+              const double pqo = fma(xb[c], q[c], pqo_acc);
+              rr_acc = own_rr ? rr : rr_acc;
+              pqo_acc = own_pq ? pqo : pqo_acc;
+              r[c] = rc;
+            }
+            if (!RDER) stw2<NT>(own, a.r, ub, c_oe, tp2, r);
+            stw2<NT>(own, a.p_out, ub, c_oe, tp2, xb);
+          }
+          const double* fs = reinterpret_cast<const double*>(lb + (s * JT) * 512);
+#pragma unroll
+          for (int t = 0; t < TF; ++t) {
+            const double f = fs[t * 64];   // one fragment read, two MFMAs
+            acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(f, xb.x, acc[0][t], 0, 0, 0);
+            acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(f, xb.y, acc[1][t], 0, 0, 0);
+          }
+          {
+            const double f = fs[TF * 64];
+            acc4[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(f, xb.x, acc4[0], 0, 0, 0);
+            acc4[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(f, xb.y, acc4[1], 0, 0, 0);
+          }
+          if (s + kD < KS) {
+            issue(slot, s + kD);
+          } else {
+            if (s + kD == KS) load_next_strip();
+            issue(slot, s + kD - KS);
+          }
+          // the partials' chains stay in their k-step (sunk below the strip,
+          // they keep every r, p and q of it alive: 976 B of scratch at TF 6)
+          if (KIND == 1) asm volatile("" : "+v"(rr_acc), "+v"(pqo_acc));
+          __builtin_amdgcn_sched_barrier(0);   // one k-step per scheduling region
+        }
+        // epilogue: the rows of SW = 1, columns 2 n and 2 n + 1 in one store
+#pragma unroll
+        for (int t = 0; t < TF; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            stw2<false>(own, a.Y, (cbase + (int64_t)(16 * t + 4 * r) * a.inner) * 8, c_oe, tp2,
+                        gd2v{acc[0][t][r], acc[1][t][r]});
+        stw2<false>(own, a.Y, (cbase + (int64_t)16 * TF * a.inner) * 8, c_oe, tp2,
+                    gd2v{acc4[0], acc4[1]});
+        cur_next(cc);
+      }
+      sg0 = sg1;
+      continue;
+    }
 
     // load cursor: strip lc, its base; past the segment the last strip again
     Cur lc = cur_at(sg0);
@@ -1806,33 +1980,45 @@ static blk_mode_fn mode_fn(int JT, bool T4) {
   }
 #undef GG_BLK_MODE
 }
-template <int KIND>
+template <int KIND, int SW = 1>
 static blk_mode_fn mode_fast_fn(int JT) {
   // the fused kinds ring kD k-steps of three operands, kD | KS: KS = 13 / 17
   // (JT 4 / 5) are prime, the whole strip in flight spills -- the generic
   // kernel there (JT 5: KIND 1 / 3 52 B of scratch, KIND 2 404 B; JT 4 KIND 2 88 B)
   if (KIND != 0 && (JT == 5 || (KIND == 2 && JT == 4))) return nullptr;
   switch (JT) {
-    case 2: return blk_mode_fast_kernel<1, KIND>;
-    case 3: return blk_mode_fast_kernel<2, KIND>;
-    case 4: return blk_mode_fast_kernel<3, KIND>;
-    case 5: return blk_mode_fast_kernel<4, KIND>;
-    case 6: return blk_mode_fast_kernel<5, KIND>;
-    case 7: return blk_mode_fast_kernel<6, KIND>;
+    case 2: return blk_mode_fast_kernel<1, KIND, SW>;
+    case 3: return blk_mode_fast_kernel<2, KIND, SW>;
+    case 4: return blk_mode_fast_kernel<3, KIND, SW>;
+    case 5: return blk_mode_fast_kernel<4, KIND, SW>;
+    case 6: return blk_mode_fast_kernel<5, KIND, SW>;
+    case 7: return blk_mode_fast_kernel<6, KIND, SW>;
     default: return nullptr;
   }
 }
+// the fast kernel of a kind (one strip per wave, or two where sw = 2)
+static blk_mode_fn mode_fast_of(int kind, int JT, int sw) {
+  if (sw == 2)
+    return kind == 5   ? mode_fast_fn<5, 2>(JT)
+           : kind == 3 ? mode_fast_fn<3, 2>(JT)
+           : kind == 1 ? mode_fast_fn<1, 2>(JT)
+           : kind == 0 ? mode_fast_fn<0, 2>(JT)
+                       : nullptr;
+  return kind == 5   ? mode_fast_fn<5>(JT)
+         : kind == 4 ? mode_fast_fn<4>(JT)
+         : kind == 3 ? mode_fast_fn<3>(JT)
+         : kind == 1 ? mode_fast_fn<1>(JT)
+         : kind == 2 ? mode_fast_fn<2>(JT)
+                     : mode_fast_fn<0>(JT);
+}
 // the fast (fixed-count) kernel where instantiated: a 4-row tail and
 // h = 16 (JT - 1) + 4 exactly (KS = 4 JT - 3)
-static blk_mode_fn select_mode(int kind, int JT, bool T4, int h = 0, bool fast = false) {
+static blk_mode_fn select_mode(int kind, int JT, bool T4, int h = 0, bool fast = false,
+                               int sw = 1) {
   if (T4 && h == 16 * (JT - 1) + 4 && fast) {
-    const blk_mode_fn f = kind == 5   ? mode_fast_fn<5>(JT)
-                          : kind == 4 ? mode_fast_fn<4>(JT)
-                          : kind == 3 ? mode_fast_fn<3>(JT)
-                          : kind == 1 ? mode_fast_fn<1>(JT)
-                          : kind == 2 ? mode_fast_fn<2>(JT)
-                                      : mode_fast_fn<0>(JT);
+    const blk_mode_fn f = mode_fast_of(kind, JT, sw);
     if (f != nullptr) return f;
+    GG_REQUIRE(sw == 1, GG_ERR_RUNTIME, "no two-strip block mode kernel for this launch");
   }
   // kind 3 (the non-temporal prologue) exists on the fast kernel only
   return (kind == 1 || kind == 3) ? mode_fn<1>(JT, T4)
@@ -1901,13 +2087,23 @@ static int blk_cus() {
   return n;
 }
 
+// strips per wave of the launch of `kind` on axis k: 2 where the fast kernel
+// runs, the kind's bit of GG_BLK_MODE_STRIPS is on and a two-strip kernel exists
+static int mode_sw(int kind, const BlockOp* B, int k) {
+  const int JT = B->JT[k];
+  if (!(B->T4[k] && B->h[k] == 16 * (JT - 1) + 4 && B->fast)) return 1;
+  const int bit = kind == 0 ? 1 : (kind == 1 || kind == 3 || kind == 5) ? 2 : 0;
+  if ((B->strips & bit) == 0) return 1;
+  return mode_fast_of(kind, JT, 2) != nullptr ? 2 : 1;
+}
+
 static void blk_set_lds_limits(const BlockOp* B) {
   for (int k = 0; k + 2 < B->d; ++k) {
     const size_t bytes = (size_t)B->KS[k] * B->JT[k] * 64 * sizeof(double);
     for (int kind = 0; kind < 6; ++kind)
       GG_HIP(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(
-              select_mode(kind, B->JT[k], B->T4[k], (int)B->h[k], B->fast)),
+          reinterpret_cast<const void*>(select_mode(kind, B->JT[k], B->T4[k], (int)B->h[k],
+                                                    B->fast, mode_sw(kind, B, k))),
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   }
 }
@@ -1954,6 +2150,8 @@ BlockOp* block_create(int d, const int64_t* rows, const int64_t* cols,
     B->cus = blk_cus();
     const char* fe = gg::knob("GG_BLK_MODE_FAST");   // A/B knob, read at creation only
     B->fast = !(fe && atoi(fe) == 0);
+    const char* st = gg::knob("GG_BLK_MODE_STRIPS");   // A/B knob, read at creation only
+    if (st) B->strips = atoi(st) & 3;   // bits above the two defined ones are ignored
     const char* ne = gg::knob("GG_BLK_PRO_NT");      // A/B knob, read at creation only
     B->pro_nt = !(ne && atoi(ne) == 0);
     const char* ee = gg::knob("GG_BLK_EPI_NT");      // A/B knob, read at creation only
@@ -2085,18 +2283,16 @@ void block_fold(const BlockOp* B, bool inverse, const double* x, double* y, doub
 static int mode_waves(int kind, const BlockOp* B, int k) {
   const int JT = B->JT[k];
   const bool fast = B->T4[k] && B->h[k] == 16 * (JT - 1) + 4 && B->fast &&
-                    (kind == 5   ? mode_fast_fn<5>(JT)
-                     : kind == 4 ? mode_fast_fn<4>(JT)
-                     : kind == 3 ? mode_fast_fn<3>(JT)
-                     : kind == 1 ? mode_fast_fn<1>(JT)
-                     : kind == 2 ? mode_fast_fn<2>(JT)
-                                 : mode_fast_fn<0>(JT)) != nullptr;
+                    mode_fast_of(kind, JT, 1) != nullptr;
   if (!fast) return kBlkModeWaves;
+  if (kind == 0 && mode_sw(kind, B, k) == 2) return fast_waves<0, 2>();
   return kind == 0 ? fast_waves<0>() : kind == 2 ? fast_waves<2>() : fast_waves<1>();
 }
 
+// sw: strips per wave (mode_sw); spb, gpb and the groups then count windows
+// of sw strips, a row's last one half empty where its strip count is odd
 static int64_t mode_geometry(const BlockOp* B, int k, int W, ModeArgs& a, int* grid_out,
-                             int64_t nblk = -1) {
+                             int64_t nblk = -1, int sw = 1) {
   const int d = B->d;
   int64_t inner = 1, outer = 1;
   for (int i = k + 1; i < d; ++i) inner *= B->e[i];
@@ -2105,7 +2301,7 @@ static int64_t mode_geometry(const BlockOp* B, int k, int W, ModeArgs& a, int* g
   a.h = (int)B->h[k];
   a.KS = B->KS[k];
   a.inner = inner;
-  a.spb = outer * (inner / 16);
+  a.spb = outer * ceil_div(inner / 16, (int64_t)sw);
   a.gpb = ceil_div(a.spb, (int64_t)W);
   a.ngroups = a.gpb * (nblk < 0 ? ((int64_t)1 << d) : nblk);
   const int64_t grid = std::min<int64_t>(a.ngroups, (int64_t)B->cus);
@@ -2123,8 +2319,12 @@ int64_t block_prologue_blocks(const BlockOp* B) {
   ModeArgs a{};
   int g = 0;
   if (B->d < 3) return 1;
+  // the capacity of the partial arrays, a bound on every prologue launch's
+  // workgroups: the CG's may run one or two strips per wave, a rank a block
+  // range, and ceil(groups / per_wg) is not monotonic in
+  // the groups; each launch reports its own count (MpFuse::pro_blocks)
   mode_geometry(B, 0, mode_waves(1, B, 0), a, &g);
-  return g;
+  return std::min<int64_t>(a.ngroups, (int64_t)B->cus);
 }
 
 // workgroups of the pair launch: blk_pair_kernel 2 slabs each, 2 per CU;
@@ -2205,7 +2405,8 @@ void block_apply(const BlockOp* B, const double* x, double* y, double shift, dou
     else if (k == 1 && side && !pair_side)
       kind = 2;
     const int W = mode_waves(kind, B, k);
-    mode_geometry(B, k, W, a, &grid, nblk);
+    const int sw = mode_sw(kind, B, k);
+    mode_geometry(B, k, W, a, &grid, nblk, sw);
     a.blk0 = blk0;
     a.X = src;
     a.Y = chain;
@@ -2244,7 +2445,8 @@ void block_apply(const BlockOp* B, const double* x, double* y, double shift, dou
       GG_REQUIRE(a.sstep <= 128 * (int64_t)a.KS, GG_ERR_VALUE,
                  "block CG: x side job larger than its k-steps");
     }
-    const blk_mode_fn fn = select_mode(kind, B->JT[k], B->T4[k], (int)B->h[k], B->fast);
+    const blk_mode_fn fn =
+        select_mode(kind, B->JT[k], B->T4[k], (int)B->h[k], B->fast, sw);
     const size_t lds = (size_t)B->KS[k] * B->JT[k] * 64 * sizeof(double);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * W), lds, stream, a);
     GG_LAUNCH_CHECK();

@@ -118,7 +118,17 @@ int gg_kron_matvec_timed(const gg_kron* K, int transpose, const double* x_dev, d
  * Lanczos probe take the block basis by default on one GPU where it is
  * unpadded (padded slabs measured slower than the grid basis there); the
  * block-sharded CG wherever it exists (no exchange between ranks).  No reference counterpart: an execution detail of
- * kron_matrix.py:52-97.                                                     */
+ * kron_matrix.py:52-97.
+ * Switches of the block kernels, all latched at gg_kron_create /
+ * gg_knobs_reload and never read on a launch path: GG_BLK_MODE_FAST (1: the
+ * fixed-count mode kernels where h = 16 TF + 4), GG_BLK_MODE_STRIPS (a mask,
+ * default 3: those kernels with two 16-column strips per wave, 16-byte
+ * accesses and two MFMAs per fragment read -- bit 0 the plain mode launches,
+ * bit 1 the CG prologues; 0: one strip per wave; higher bits are ignored;
+ * every vector a launch writes is bitwise the same either way, only the
+ * prologues' partial sums group over another grid), GG_BLK_PRO_NT,
+ * GG_BLK_EPI_NT (1: non-temporal CG streams), GG_BLK_PAIR_LDS,
+ * GG_BLK_PAIR_SPW (1, 2: the LDS pair kernel, its slabs per workgroup).      */
 int gg_kron_block_info(const gg_kron* K, int* available, int64_t* n, int* launches);
 /* y = P x (inverse: x = P^T y, the unfold); x, y distinct: the grid vector
  * (the operator's n) and the block-layout vector (gg_kron_block_info's n).  */
