@@ -612,7 +612,9 @@ int gg_cgm_status(gg_cgm* c, int* iters, int* converged, double* resid_norm, dou
     GG_HIP(hipStreamSynchronize(s));
     const gg::CgmScalars& h = *c->sc_host;
     if (iters) *iters = h.iters;
-    if (converged) *converged = (h.done && std::sqrt(h.rr) < h.tol) || h.bnorm == 0.0;
+    // a created, unstarted handle holds zeroed scalars (bnorm == 0): not converged
+    if (converged)
+      *converged = c->x != nullptr && ((h.done && std::sqrt(h.rr) < h.tol) || h.bnorm == 0.0);
     if (resid_norm) *resid_norm = std::sqrt(h.rr);
     if (tol) *tol = h.tol;
   });

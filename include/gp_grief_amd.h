@@ -420,13 +420,24 @@ int gg_cgm_set_precond(gg_cgm* cgm, const gg_kron* Q, const double* lam_dev);
  * a NULL handle, a call after gg_cgm_start, a misaligned noise_dev.         */
 int gg_cgm_set_noise(gg_cgm* cgm, const double* noise_dev);
 /* r = select(mask, b, 0), x = 0, tolerance max(atol, rtol |W b|).  b_dev and
- * x_dev at any 8-byte aligned address (16-byte: the double2 kernels).       */
+ * x_dev at any 8-byte aligned address (16-byte: the double2 kernels).  A
+ * started handle may be started again (another b, x or tolerance): the solve
+ * is that of a fresh handle with the same settings, bit for bit.
+ * GG_ERR_VALUE, x untouched and the handle as it was: a NULL argument, a
+ * negative or NaN rtol or atol (rtol = atol = 0 is accepted: the iteration
+ * then stops only at |r| = 0 or NaN).                                       */
 int gg_cgm_start(gg_cgm* cgm, const double* b_dev, double* x_dev, double rtol, double atol,
                  gg_stream stream);
-/* Up to max_iters iterations; the host polls the device's done flag every
- * check_every iterations (<= 0: never) and stops issuing work once it is set;
- * successive calls continue the same recurrence.                            */
+/* Up to max_iters iterations (<= 0: nothing is done, GG_OK); the host polls
+ * the device's done flag every check_every iterations (<= 0: never) and stops
+ * issuing work once it is set; the polling changes neither the iteration at
+ * which the device stops nor a bit of x.  Successive calls continue the same
+ * recurrence; calls after it has stopped (converged, or a NaN residual)
+ * change neither x nor the iteration count.  GG_ERR_VALUE before
+ * gg_cgm_start.                                                             */
 int gg_cgm_iterate(gg_cgm* cgm, int max_iters, int check_every, gg_stream stream);
+/* Each output pointer may be NULL.  Before gg_cgm_start: iters = 0,
+ * converged = 0.                                                            */
 int gg_cgm_status(gg_cgm* cgm, int* iters, int* converged, double* resid_norm, double* tol,
                   gg_stream stream); /* synchronising */
 
@@ -493,7 +504,9 @@ int gg_lanczos_info(const gg_kron* K, int* block, int* launches);
  * betas[k] go to host memory (the one synchronisation); breakdown and
  * *steps_done as gg_lanczos_probe.  GG_ERR_VALUE for a NULL mask, a
  * non-square operator or factors, steps < 1, shift < 0 (all before any
- * launch) or a mask with no observed point.                                  */
+ * launch, the host outputs untouched) or a mask with no observed point
+ * (found after the run: *n_observed = 0 is written, the arrays and
+ * *steps_done are not; the same for the timed entry).                        */
 int gg_lanczos_probe_masked(const gg_kron* K, double shift, const uint8_t* mask_dev,
                             uint64_t seed, int probe, int steps, double* work_dev,
                             double* alphas_host, double* betas_host, int* steps_done,

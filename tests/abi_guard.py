@@ -1,6 +1,7 @@
-"""The guarded device buffer of the C ABI edge tests (test_gpu_kron_abi.py,
-test_gpu_shard_abi.py): a payload of exactly the documented size between two
-guards of 64 NaN doubles, compared bit for bit."""
+"""The guarded device buffers of the C ABI edge tests (test_gpu_kron_abi.py,
+test_gpu_shard_abi.py, test_gpu_masked_abi.py): a payload of exactly the
+documented size between two guards of 64 NaN doubles (Guard) or, for a byte
+mask, 64 bytes of 0xFF (ByteGuard), compared bit for bit."""
 import ctypes
 
 import numpy as np
@@ -55,3 +56,30 @@ class Guard(object):
         torch.cuda.synchronize()
         self.d.copy_(torch.from_numpy(self.h0))
         torch.cuda.synchronize()
+
+
+class ByteGuard(object):
+    """The byte twin for masks: a payload of exactly n bytes on the device
+    between two guards of 64 bytes of 0xFF (nonzero: a read past either end
+    sees an observed point), the payload `off` (0 or 1) bytes past a 16-byte
+    boundary.  An input only: unchanged() is its one check."""
+
+    def __init__(self, data, off=0):
+        import torch
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        self.n, self.off = data.size, int(off)
+        self.lo = self.off + GUARD
+        h = np.full(self.lo + self.n + GUARD, 0xFF, dtype=np.uint8)
+        h[self.lo:self.lo + self.n] = data
+        self.h0 = h
+        self.d = torch.from_numpy(h.copy()).cuda()
+        assert self.d.data_ptr() % 16 == 0
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.d.data_ptr() + self.lo)
+
+    def unchanged(self):
+        import torch
+        torch.cuda.synchronize()
+        assert np.array_equal(self.d.cpu().numpy(), self.h0), "the mask was written"

@@ -165,8 +165,10 @@ def test_masked_kron_cg_chunking(gg, precond):
     b.iterate(30, check_every=7)
     sa, sb = a.status(), b.status()
     assert sa[0] == 30 and sb[0] == 30 and not sa[1]
-    assert rel(a.x.cpu().numpy(), b.x.cpu().numpy()) < 1e-12
-    assert abs(sa[2] - sb[2]) <= 1e-12 * sb[2]
+    # the same launch sequence whatever the chunking: the same bits
+    # (test_gpu_masked_abi.py pins it for the C ABI)
+    assert np.array_equal(a.x.cpu().numpy(), b.x.cpu().numpy())
+    assert sa[2] == sb[2]
     assert a.n_observed == int(mask.sum())
 
 
