@@ -28,6 +28,10 @@ Device solvers (no reference implementation exists):
 Every one of the masked solvers takes noise=: per-point noise variances, the
 system W K W + diag(noise) (gg_cgm_set_noise, gg_lanczos_probe_masked_noise,
 gg_sample_residual_noise).
+  LaplaceNewton -- the mode of a Laplace approximation with a Poisson or
+                   binomial likelihood on the grid: Newton steps whose solve is
+                   the weighted masked CG with noise 1 / w, the likelihood as
+                   one fused streaming pass (gg_lik_newton).
 """
 import ctypes
 import logging
@@ -987,3 +991,173 @@ class GridPosteriorSampler(object):
         mean *= scale
         m2 *= scale * scale / (S - 1)
         return mean, m2
+
+
+# ------------------------------------------------- Laplace approximation
+LIKELIHOODS = {"poisson": 0, "binomial": 1}
+
+
+def likelihood_constant(kind, y, aux, mask):
+    """The f-independent part of sum_o log p (host; once per model): Poisson
+    sum y log e - lgamma(y + 1), binomial sum lgamma(t + 1) - lgamma(y + 1) -
+    lgamma(t - y + 1) over the observed points -- what gg_lik_newton leaves out
+    of its sums[0]."""
+    from scipy.special import gammaln
+    m = np.asarray(mask).reshape(-1) != 0
+    y = np.asarray(y, dtype=np.float64).reshape(-1)[m]
+    e = np.ones(y.size) if aux is None else np.asarray(aux, dtype=np.float64).reshape(-1)[m]
+    if kind == LIKELIHOODS["poisson"]:
+        return float(np.sum(y * np.log(e) - gammaln(y + 1)))
+    return float(np.sum(gammaln(e + 1) - gammaln(y + 1) - gammaln(e - y + 1)))
+
+
+class LaplaceNewton(object):
+    """The mode of psi(a) = sum_o log p(y_i | f_i) - 1/2 a^T K a, f = K a, for a
+    log-concave likelihood on the grid ('poisson', log link; 'binomial', logit
+    link): Newton's method in the (K + W^-1) form (Rasmussen & Williams Alg.
+    3.1) on one MI355X.
+
+    A step from a: b = select(mask, f + g / w, 0) and noise = 1 / w by one fused
+    pass (gg_lik_newton), a_full = (W_mask K W_mask + diag(noise))^-1 b by the
+    weighted masked CG from x0 = 0, then a <- a + s (a_full - a) with s = 1,
+    halved (at most max_halvings times) while psi does not rise; each trial is
+    one axpy, one Kronecker matvec and one read-only gg_lik_newton, whose five
+    sums (40 bytes) are the only thing the host reads.  The solver is ONE
+    MaskedKronCG built on the noise buffer: the handle keeps the pointer and
+    the CG's kernels read the buffer afresh every iteration (gg_cgm_set_noise
+    caches nothing derived from it), so a step rewrites it in place and solves
+    again.  Its positivity check runs once, on the noise of a = 0.
+
+    Stop rule: converged when |(g - a)_o| <= newton_tol max(1, |g_o|) (a = g at
+    the mode); stalled when an accepted step raised psi by less than 1e-14
+    |psi|, or no halving raised it -- psi's double-precision resolution, which
+    a large Poisson problem reaches near a relative residual of 1e-9.  A trial
+    that meets the stop rule is accepted whatever psi says: psi is concave, so
+    a = g to the tolerance identifies the mode, while the last quadratic step
+    gains about |g - a|^2, which the rounding of psi's sums hides once the
+    residual is near 1e-6.
+
+    y, aux (exposure / trials; None = 1), mask: N entries, numpy or device;
+    values at the missing points are never used (NaN allowed).  const: the
+    likelihood's f-independent normaliser (likelihood_constant), added to psi.
+    precond='kron' goes to the solver; its scalar stand-in for the noise is
+    the geometric mean of the noise at a = 0 and stays fixed over the steps --
+    a heuristic whose effect on the iteration count has not been measured.
+
+    mode(a0=None) runs the iteration (a0: a warm start, zeroed at the missing
+    points) and leaves a, f, noise, b (device), psi, sum_log_w, newton_iters,
+    newton_converged, newton_stalled, cg_iters (one entry per step) and
+    halvings on the object.
+    """
+
+    def __init__(self, K, y, likelihood, aux=None, mask=None, precond=None, cg_rtol=1e-10,
+                 newton_tol=1e-8, max_newton=50, max_halvings=20, const=0.0):
+        from . import device as dev
+        from . import native
+        if likelihood not in LIKELIHOODS:
+            raise ValueError("likelihood must be 'poisson' or 'binomial', not %r" % (likelihood,))
+        self.kind = LIKELIHOODS[likelihood]
+        self.K = K
+        self.n = n = int(K.shape[0])
+        t = dev.torch()
+        self.mask = _all_ones_mask(n) if mask is None else _mask_to_device(mask, n)[0]
+        self.y = dev.ensure_aligned(dev.to_device(y))
+        self.aux = None if aux is None else dev.ensure_aligned(dev.to_device(aux))
+        if self.y.numel() != n or (self.aux is not None and self.aux.numel() != n):
+            raise ValueError("y and aux must have %d entries" % n)
+        self.cg_rtol, self.newton_tol = float(cg_rtol), float(newton_tol)
+        self.max_newton, self.max_halvings = int(max_newton), int(max_halvings)
+        self.const = float(const)
+        self.noise, self.b = dev.empty(n), dev.empty(n)
+        self.a, self.f = dev.zeros(n), dev.zeros(n)
+        self._a_try, self._f_try, self._x = dev.empty(n), dev.empty(n), dev.empty(n)
+        self._sums = t.zeros(5, dtype=t.float64, device=self.a.device)
+        self._partials = dev.empty(native.GG_LIK_PARTIALS)
+        # the noise of a = 0 (f = 0): what the solver's one positivity check sees
+        self._pass(self.f, self.a, write=True)
+        self.solver = MaskedKronCG(K, None, self.mask, precond=precond, noise=self.noise)
+        self.newton_iters, self.newton_converged, self.newton_stalled = 0, False, False
+        self.cg_iters, self.halvings = [], []
+        self.psi = self.sum_log_w = None
+
+    def set_operator(self, K):
+        """Another K of the same factor orders (new hyperparameters): a new
+        solver on the same noise buffer; a and f stay for the warm start."""
+        if int(K.shape[0]) != self.n:
+            raise ValueError("K must have %d rows" % self.n)
+        self.K = K
+        self.solver = MaskedKronCG(K, None, self.mask, precond=self.solver.precond,
+                                   noise=self.noise, precond_shift=self.solver.shift)
+
+    def _pass(self, f, a, write):
+        """gg_lik_newton at (f, a): the five sums on the host."""
+        from . import native
+        native.check(native.lib().gg_lik_newton(
+            self.kind, native.dptr(self.y), None if self.aux is None else native.dptr(self.aux),
+            native.dptr(f), native.dptr(a), ctypes.c_void_p(self.mask.data_ptr()),
+            native.dptr(self.noise) if write else None, native.dptr(self.b) if write else None,
+            native.dptr(self._sums), native.dptr(self._partials), self.n, native.stream_ptr()),
+            "gg_lik_newton")
+        return self._sums.cpu().numpy()
+
+    def _stop(self, sums):
+        # on finite sums only: an overflowed trial has inf <= inf
+        return bool(np.all(np.isfinite(sums))
+                    and np.sqrt(sums[3]) <= self.newton_tol * max(1.0, np.sqrt(sums[4])))
+
+    def mode(self, a0=None):
+        from . import dense
+        from . import device as dev
+        t = dev.torch()
+        if a0 is None:
+            self.a.zero_()
+        else:
+            a0 = dev.to_device(a0)
+            if a0.numel() != self.n:
+                raise ValueError("a0 must have %d entries" % self.n)
+            t.where(self.mask != 0, a0, t.zeros_like(a0), out=self.a)
+        K = self.K
+        K.matvec_device(self.a, out=self.f)
+        sums = self._pass(self.f, self.a, write=True)
+        psi = sums[0] + self.const - 0.5 * sums[1]
+        self.newton_iters, self.newton_converged, self.newton_stalled = 0, False, False
+        self.cg_iters, self.halvings = [], []
+        small_gain = False
+        with np.errstate(invalid="ignore"):
+            while True:
+                if self._stop(sums):
+                    self.newton_converged = True
+                    break
+                if small_gain or self.newton_iters >= self.max_newton:
+                    self.newton_stalled = small_gain
+                    break
+                x, it, conv = self.solver.solve(self.b, rtol=self.cg_rtol, x_out=self._x)[:3]
+                if not conv:
+                    logger.info('Laplace Newton step %d: CG did not converge in %d iterations'
+                                % (self.newton_iters, it))
+                self.cg_iters.append(it)
+                dense.axpby(-1.0, self.a, 1.0, x)    # the full step's direction
+                s, accepted = 1.0, False
+                for h in range(self.max_halvings + 1):
+                    self._a_try.copy_(self.a)
+                    dense.axpby(s, x, 1.0, self._a_try)
+                    K.matvec_device(self._a_try, out=self._f_try)
+                    sums_try = self._pass(self._f_try, self._a_try, write=False)
+                    psi_try = sums_try[0] + self.const - 0.5 * sums_try[1]
+                    if psi_try > psi or self._stop(sums_try):
+                        accepted = True
+                        break
+                    s *= 0.5
+                if not accepted:
+                    self.newton_stalled = True
+                    break
+                self.halvings.append(h)
+                small_gain = psi_try - psi < 1e-14 * abs(psi_try)
+                self.a, self._a_try = self._a_try, self.a
+                self.f, self._f_try = self._f_try, self.f
+                psi = psi_try
+                sums = self._pass(self.f, self.a, write=True)
+                self.newton_iters += 1
+        self.psi, self.sum_log_w = float(psi), float(sums[2])
+        self.sums = sums
+        return self.a

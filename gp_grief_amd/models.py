@@ -20,6 +20,11 @@
                  (Schur identity), scaled-eigenvalue or masked-SLQ
                  (logdet='lanczos') log det, imputed grid mean, off-grid mean
                  and variance.
+  GPGridLaplaceModel  (new) the grid GP with Poisson / binomial observations
+                 by the Laplace approximation: Newton on the weighted masked
+                 CG (linalg.LaplaceNewton), Laplace LML with the weighted SLQ
+                 log det, GPGridModel's posterior machinery on the
+                 pseudo-targets, response-scale moments.
 
 Device state keeps the reference's attribute names (_Phi, _A, _P, _Pchol,
 _alpha, _alpha_p) holding CUDA tensors (or small host arrays where the
@@ -741,6 +746,10 @@ class GPGridModel(BaseModel):
     Matheron's rule with e_i ~ N(0, noise_var * noise_scale[i]).
     """
 
+    # predict(Xnew) on an incomplete grid adds noise_var to the variance
+    # (GPGridLaplaceModel: the latent variance, nothing added)
+    _predict_adds_noise = True
+
     def __init__(self, xg, Y, kern, noise_var=1., solver=None, logdet='exact',
                  dim_noise_var=1e-12, cg_rtol=1e-10, slq_probes=8, slq_steps=50, seed=0,
                  mask=None, precond=None, exact_missing_max=1024,
@@ -1185,7 +1194,7 @@ class GPGridModel(BaseModel):
             for j in range(Xnew.shape[0]):
                 ks = self._kron_row([Af[j, :] for Af in A])
                 v = solver.solve(ks, rtol=self.cg_rtol)[0]
-                var[j] = kss - dense.dot(ks, v) + s
+                var[j] = kss - dense.dot(ks, v) + (s if self._predict_adds_noise else 0.0)
             return dense.host(mean).reshape(-1, 1), var.reshape(-1, 1)
         Q, T = self._schur()
         V2 = []
@@ -1206,6 +1215,173 @@ class GPGridModel(BaseModel):
         kss = float(self.kern.diag_val)
         var = kss - dense.host(quad) + s
         return dense.host(mean).reshape(-1, 1), var.reshape(-1, 1)
+
+
+class GPGridLaplaceModel(GPGridModel):
+    """Grid GP with a non-Gaussian, log-concave likelihood by the Laplace
+    approximation: counts, y_i ~ Poisson(e_i exp f_i)
+    (likelihood='poisson', exposure= e, default 1 -- the log-Gaussian Cox
+    process on a grid), or successes, y_i ~ Binomial(t_i, sigma(f_i))
+    (likelihood='binomial', trials= t, default 1: Bernoulli).  y need not be
+    integer (fractional pseudo-counts are legitimate).  mask as GPGridModel:
+    Y, exposure and trials at the missing points are ignored (NaN allowed).
+
+    fit() finds the mode a^ of psi(a) = sum_o log p(y_i | (K a)_i) - 1/2 a^T K a
+    by linalg.LaplaceNewton (newton_tol, max_newton; the weighted masked CG to
+    cg_rtol, precond None or 'kron'), warm-started from the previous mode, and
+    reports newton_iters, newton_converged, newton_stalled and cg_iters (one
+    entry per Newton step).  The LML is Laplace's,
+    psi(a^) - 1/2 [log det(K_oo + W^-1_oo) + sum_o log w^_i], w^ = -d^2 log p /
+    d f^2 at the mode, the log determinant by the weighted masked SLQ
+    (linalg.slq_logdet(K, 0, mask=, noise=1 / w^); slq_probes, slq_steps, seed;
+    per-probe estimates in slq_estimates).  The hyperparameters are the
+    kernel's alone (noise_var is fixed at 1 and means nothing here);
+    grad_method is 'finite_difference' only -- 'adjoint' raises ValueError:
+    the mode's implicit dependence on the kernel brings a third-derivative
+    term that is not implemented.  optimize() as every model.
+
+    The Laplace posterior N(f^, (K^-1 + W^)^-1) is the Gaussian-noise posterior
+    of the pseudo-targets b^ = f^ + W^-1 g^ observed with noise 1 / w^, so the
+    inherited machinery runs on it unchanged: predict_grid(compute_var=False)
+    gives f^ = K a^ at all N points, sample_posterior / posterior_moments draw
+    the latent field by Matheron's rule, predict(Xnew) gives the latent mean
+    and the LATENT variance k** - k*^T (K_oo + W^-1)^-1 k* (nothing is added to
+    it here: there is no Gaussian observation noise to add).
+    response_moments(n_samples, seed) gives the mean and variance of the
+    response -- exp(f), the rate per unit exposure, or sigma(f), the success
+    probability -- at all N grid points.
+    """
+
+    _predict_adds_noise = False
+
+    def __init__(self, xg, Y, kern, likelihood, exposure=None, trials=None, mask=None,
+                 precond=None, cg_rtol=1e-10, newton_tol=1e-8, max_newton=50, slq_probes=8,
+                 slq_steps=50, seed=0, grad_method='finite_difference'):
+        from .linalg import LIKELIHOODS, likelihood_constant
+        if likelihood not in LIKELIHOODS:
+            raise ValueError("likelihood must be 'poisson' or 'binomial', not %r" % (likelihood,))
+        if grad_method != 'finite_difference':
+            raise ValueError("GPGridLaplaceModel: grad_method must be 'finite_difference' (the "
+                             "analytic Laplace gradient's implicit term is not implemented)")
+        if likelihood == 'poisson' and trials is not None:
+            raise ValueError("trials= belongs to likelihood='binomial'; Poisson takes exposure=")
+        if likelihood == 'binomial' and exposure is not None:
+            raise ValueError("exposure= belongs to likelihood='poisson'; binomial takes trials=")
+        aux = exposure if likelihood == 'poisson' else trials
+        n = int(np.prod([np.shape(g)[0] for g in xg]))
+        if tuple(Y.shape) != (n, 1):
+            raise ValueError('Y must be (%d,1), the flattened grid' % n)
+
+        def host(v):
+            return dev.to_host(v) if dev.is_device_array(v) else np.asarray(v, dtype=np.float64)
+
+        m = np.ones(n, dtype=bool) if mask is None else host(mask).reshape(-1) != 0
+        if m.size != n:
+            raise ValueError("mask must have %d entries, not %d" % (n, m.size))
+        yh = host(Y).reshape(-1).astype(np.float64)
+        ah = None
+        if aux is not None:
+            ah = host(aux).reshape(-1).astype(np.float64)
+            if ah.size != n:
+                raise ValueError("%s must have %d entries" %
+                                 ('exposure' if likelihood == 'poisson' else 'trials', n))
+            if not np.all(np.isfinite(ah[m]) & (ah[m] > 0)):
+                raise ValueError("%s must be positive and finite at every observed point" %
+                                 ('exposure' if likelihood == 'poisson' else 'trials'))
+        if not np.all(np.isfinite(yh[m]) & (yh[m] >= 0)):
+            raise ValueError("Y must be non-negative and finite at every observed point")
+        if likelihood == 'binomial' and np.any(yh[m] > (1.0 if ah is None else ah[m])):
+            raise ValueError("Y must not exceed trials at an observed point")
+        super(GPGridLaplaceModel, self).__init__(
+            xg, Y, kern, noise_var=1., solver='cg', logdet='lanczos', cg_rtol=cg_rtol,
+            slq_probes=slq_probes, slq_steps=slq_steps, seed=seed, mask=m, precond=precond)
+        self.noise_var_constraint = 'fixed'
+        self.likelihood = likelihood
+        self.newton_tol, self.max_newton = float(newton_tol), int(max_newton)
+        self._counts = self._yd          # Y, zero at the missing points
+        self._aux = None if ah is None else dev.to_device(np.where(m, ah, 1.0))
+        self._lik_const = likelihood_constant(LIKELIHOODS[likelihood], yh, ah, m)
+        self._newton = None
+        self.newton_iters, self.newton_converged, self.newton_stalled = 0, False, False
+        self.cg_iters = []
+        self.psi = None
+
+    def fit(self):
+        """The mode a^ (warm-started from the previous one); then _yd holds the
+        pseudo-targets b^, _nscale the noise 1 / w^ and the resident solver is
+        the Newton driver's: GPGridModel's posterior machinery runs on them."""
+        from .linalg import LaplaceNewton
+        self.parameters
+        if self._alpha is not None:
+            return
+        K = self._operator()
+        nt = self._newton
+        if nt is None:
+            nt = self._newton = LaplaceNewton(
+                K, self._counts, self.likelihood, aux=self._aux, mask=self._mask,
+                precond=self.precond, cg_rtol=self.cg_rtol, newton_tol=self.newton_tol,
+                max_newton=self.max_newton, const=self._lik_const)
+            nt.mode()
+        else:
+            if nt.K is not K:
+                nt.set_operator(K)
+            nt.mode(a0=nt.a)
+        if not nt.newton_converged:
+            logger.info('Laplace Newton %s after %d steps'
+                        % ('stalled' if nt.newton_stalled else 'did not converge',
+                           nt.newton_iters))
+        self.newton_iters, self.newton_converged = nt.newton_iters, nt.newton_converged
+        self.newton_stalled, self.cg_iters = nt.newton_stalled, list(nt.cg_iters)
+        self.psi = nt.psi
+        self._sum_log_w = nt.sum_log_w
+        self._alpha = nt.a.clone()
+        self._yd, self._nscale = nt.b, nt.noise
+        self._mcg = nt.solver
+        self._sampler_obj = None     # its right-hand side and noise have moved
+
+    def _masked_cg(self):
+        self.fit()
+        return self._newton.solver
+
+    def _compute_log_likelihood(self, parameters):
+        """Laplace's approximation to the log marginal likelihood."""
+        self.parameters = parameters
+        self.fit()
+        ll = self.psi - 0.5 * (self._cov_log_det() + self._sum_log_w)
+        return np.array([[ll]])
+
+    def _adjoint_gradient(self, parameters):
+        raise ValueError("GPGridLaplaceModel has no analytic gradient (the mode's implicit "
+                         "dependence on the kernel is not implemented); use "
+                         "grad_method='finite_difference'")
+
+    def _sampler(self, seed):
+        self.fit()
+        return super(GPGridLaplaceModel, self)._sampler(seed)
+
+    def response_moments(self, n_samples, seed=None):
+        """(mean, var), each (N, 1): the sample mean and the unbiased sample
+        variance of the response exp(f) (Poisson: the rate per unit exposure)
+        or sigma(f) (binomial: the success probability) over posterior draws
+        0 .. n_samples - 1 of `seed`, at all N grid points (missing ones
+        included).  Each Matheron draw is folded in by one pass
+        (gg_lik_response_accumulate); no draw is kept."""
+        from . import native
+        from .linalg import LIKELIHOODS
+        S = int(n_samples)
+        if S < 2:
+            raise ValueError("the sample variance needs n_samples >= 2")
+        smp = self._sampler(seed)
+        smp._streams(S - 1)
+        n = self.num_data
+        mean, m2 = dev.empty(n), dev.empty(n)
+        for k in range(S):
+            f, w = smp._terms(k)
+            native.check(native.lib().gg_lik_response_accumulate(
+                LIKELIHOODS[self.likelihood], native.dptr(f), native.dptr(w), native.dptr(mean),
+                native.dptr(m2), k + 1, n, native.stream_ptr()), "gg_lik_response_accumulate")
+        m2 /= S - 1
+        return self._out(mean), self._out(m2)
 
 
 def _content_key(a):

@@ -26,6 +26,10 @@ GG_DIAG_DIVIDE = 0
 GG_DIAG_POSTVAR = 1
 GG_DIAG_MULTIPLY = 2
 
+GG_LIK_POISSON = 0
+GG_LIK_BINOMIAL = 1
+GG_LIK_PARTIALS = 5 * 2048   # gg_lik_newton's workspace, in doubles
+
 _c_i64p = ctypes.POINTER(ctypes.c_int64)
 _c_dp = ctypes.c_void_p  # device or host double* (passed as raw addresses)
 _vp = ctypes.c_void_p
@@ -150,6 +154,10 @@ SIGNATURES = {
                                  ctypes.c_int64, _vp],
     "gg_sample_accumulate": [_c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int64,
                              _vp],
+    "gg_lik_newton": [ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp,
+                      ctypes.c_int64, _vp],
+    "gg_lik_response_accumulate": [ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int,
+                                   ctypes.c_int64, _vp],
     "gg_sym_eig_batched": [ctypes.c_int, _c_i64p, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
                            ctypes.c_int, _vp],
     "gg_sym_eig_work_elems": [ctypes.c_int, _c_i64p, _c_i64p],

@@ -603,6 +603,64 @@ int gg_sample_residual_noise(const double* y_dev, const double* f_dev, const dou
 int gg_sample_accumulate(const double* f_dev, const double* w_dev, double* out_dev,
                          double* mean_dev, double* m2_dev, int k, int64_t n, gg_stream s);
 
+/* ------------------- non-Gaussian likelihoods: the Laplace approximation
+ * (gg_lik.hip; no reference counterpart).  A log-concave likelihood p(y | f)
+ * on the grid, f = K a: the Newton step of the mode search is a solve with
+ * W K W + diag(1 / w), w = -d^2 log p / d f^2 > 0 -- gg_cgm_set_noise's
+ * operator, with the right-hand side select(mask, f + g / w, 0), g = d log p /
+ * d f.  The passes below are what lies between the Kronecker matvec and that
+ * solve.  aux is the exposure e (Poisson) or the number of trials t
+ * (binomial), NULL = 1 everywhere:
+ *   GG_LIK_POISSON   rate e exp(f):  g = y - e exp(f),  w = e exp(f),
+ *                    core log p = y f - e exp(f)
+ *   GG_LIK_BINOMIAL  y of t, logit:  g = y - t sigma(f), w = t sigma(f) sigma(-f),
+ *                    core log p = y f - t log(1 + exp f)
+ * "core": log p without its normaliser, which does not depend on f (Poisson:
+ * y log e - lgamma(y + 1); binomial: lgamma(t + 1) - lgamma(y + 1) - lgamma(t
+ * - y + 1)).  The caller adds the sum of the normalisers over the observed
+ * points, a per-model constant, to sums[0]; no lgamma runs on the device.
+ * exp is only ever taken of a clamped or non-positive argument (binomial:
+ * exp(-|f|), log1p(exp(-|f|))).  For |f| <= 700 the noise 1 / w is finite and
+ * positive (aux within [1e-4, 1e4]); beyond, f is clamped to +-700 where w
+ * and its derived outputs (noise_out, log w, the g / w term of b_out) are
+ * formed, and only there: g and log p use f as given (a Poisson rate may then
+ * overflow to inf, which the caller's line search rejects).                  */
+#define GG_LIK_POISSON 0
+#define GG_LIK_BINOMIAL 1
+/* One fused streaming pass over n points.  Reads y, aux (NULL = 1), f, a and
+ * mask_dev (n bytes, any alignment; NULL = every point observed); writes
+ * noise_out[i] = 1 / w_i and b_out[i] = f_i + g_i / w_i at the observed points
+ * and noise_out[i] = 1, b_out[i] = 0 at the missing ones (the buffer stays a
+ * valid noise vector), and reduces over the observed points into
+ * sums_dev[0..4] (device):  sum core log p,  sum a_i f_i,  sum log w_i,
+ * sum (g_i - a_i)^2,  sum g_i^2.  noise_out == b_out == NULL is the read-only
+ * form (the objective of a trial step): the same five sums, bit for bit those
+ * of the write form at the same lane width, nothing else written.  At a
+ * missing point y, aux and everything derived from f are selected away, never
+ * multiplied by 0: NaN there reaches no output.
+ * partials_dev: 5 x 2048 doubles of workspace.  Two launches (the pass on up
+ * to 2048 workgroups, a one-block finish), no atomics: the sums are
+ * deterministic for a given n and lane width.  Lanes: 16 bytes where every
+ * vector of the call is 16-byte aligned, else 8 bytes for the whole pass (the
+ * rule of gg_cgm_set_noise); the element outputs are the same bits either
+ * way.  n == 0 zeroes the sums.  GG_ERR_VALUE, nothing written: an unknown
+ * kind, a NULL y_dev / f_dev / a_dev / sums_dev, n < 0, exactly one of
+ * noise_out / b_out NULL, a NULL partials_dev with n > 0, a vector that is
+ * not 8-byte aligned.                                                         */
+int gg_lik_newton(int kind, const double* y_dev, const double* aux_dev, const double* f_dev,
+                  const double* a_dev, const uint8_t* mask_dev, double* noise_out,
+                  double* b_out, double* sums_dev, double* partials_dev, int64_t n,
+                  gg_stream s);
+/* The response of a latent draw x = f + w (Matheron: the prior draw plus K
+ * alpha): r = exp(x), the Poisson rate per unit exposure, or sigma(x), the
+ * binomial probability, folded into Welford's running moments as draw number
+ * k with the contract of gg_sample_accumulate (k == 1 initialises mean_dev and
+ * m2_dev; after k draws mean is the sample mean, m2 / (k - 1) the unbiased
+ * variance).  One pass, no draw kept.  GG_ERR_VALUE, nothing written: an
+ * unknown kind, a NULL pointer, n < 0, k < 1.                                 */
+int gg_lik_response_accumulate(int kind, const double* f_dev, const double* w_dev,
+                               double* mean_dev, double* m2_dev, int k, int64_t n, gg_stream s);
+
 /* --------------------------------------- per-factor symmetric eigensolver
  * KronMatrix.schur / svd / eig_vals per factor   kron_matrix.py:161-200, 355-366
  * Householder tridiagonalisation + implicit QL on device, one workgroup per
