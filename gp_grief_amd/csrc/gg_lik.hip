@@ -13,11 +13,13 @@
 // The element arithmetic is one function (lik_point) whatever the lanes, so
 // the element outputs do not depend on the alignment.
 //
-// Transcendentals per observed point: one exp (Poisson), one exp and two
-// log1p (binomial; one where |f| <= 700), one log of aux only when aux is
-// given (sum log w); divisions: one (Poisson, write form), three (binomial,
-// one in the read-only form).  lgamma is not here: the normaliser of log p
-// does not depend on f and stays on the host (include/gp_grief_amd.h).
+// Transcendentals per observed point: one exp (Poisson; a second where |f| >
+// 700, for the rate at the unclamped f), one exp and two log1p (binomial; one
+// log1p where |f| > 700; the write form besides a two-term exp(f) for f >= 0,
+// about 60 multiply-adds and no division), one log of aux only when aux is
+// given (sum log w); divisions: one (Poisson, write form), two (binomial, one
+// in the read-only form).  lgamma is not here: the normaliser of log p does
+// not depend on f and stays on the host (include/gp_grief_amd.h).
 //
 // gg_lik_response_accumulate: r = exp(f + w) or sigmoid(f + w) folded into
 // Welford's moments, the contract of gg_sample_accumulate.
@@ -35,6 +37,53 @@ constexpr int kLikSums = 5;
 // or g): exp(-700) ~ 1e-304 keeps 1 / w finite
 constexpr double kLikClamp = 700.0;
 
+// exp(x) for 0 <= x <= 700 as an unevaluated sum hi + lo, to about 2^-66 of
+// its value: x = k ln 2 + r with ln 2 in three parts (k L1 is exact), exp(r / 8)
+// as 1 + q + q^2 / 2 in two-term arithmetic plus the Taylor tail from q^3 on in
+// plain double (|q| <= 0.044: the tail is below 2^-16 of the sum), squared
+// three times, scaled by 2^k.
+__device__ __forceinline__ void exp_dd(double x, double& hi, double& lo) {
+  const double k = rint(x * 0x1.71547652b82fep+0);
+  const double r1 = fma(-k, 0x1.62e42fee00000p-1, x);           // exact
+  const double p = k * 0x1.a39ef35793c76p-33;
+  const double pe = fma(k, 0x1.a39ef35793c76p-33, -p);          // k L2 = p + pe
+  double rh = r1 - p;                                           // two-sum
+  double bb = rh - r1;
+  double rl = ((r1 - (rh - bb)) - (p + bb)) - fma(k, 0x1.cc01f97b57a08p-87, pe);
+  const double qh = 0.125 * (rh + rl);
+  const double ql = 0.125 * ((rh - 8.0 * qh) + rl);
+  double t = 1.0 / 39916800.0;
+  t = fma(t, qh, 1.0 / 3628800.0);
+  t = fma(t, qh, 1.0 / 362880.0);
+  t = fma(t, qh, 1.0 / 40320.0);
+  t = fma(t, qh, 1.0 / 5040.0);
+  t = fma(t, qh, 1.0 / 720.0);
+  t = fma(t, qh, 1.0 / 120.0);
+  t = fma(t, qh, 1.0 / 24.0);
+  t = fma(t, qh, 1.0 / 6.0);
+  const double q2 = qh * qh;
+  const double q2e = fma(qh, qh, -q2);                          // qh^2 = q2 + q2e
+  const double tail = t * q2 * qh;
+  const double s1 = 1.0 + qh;                                   // fast two-sum, 1 > |qh|
+  const double e1 = qh - (s1 - 1.0);
+  const double h2 = 0.5 * q2;
+  const double s2 = s1 + h2;                                    // fast two-sum, s1 > h2
+  const double e2 = h2 - (s2 - s1);
+  double l = (e1 + e2) + (fma(qh, ql, 0.5 * q2e) + ql) + fma(ql, h2, tail);
+  double h = s2 + l;
+  l = l - (h - s2);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                                 // (h + l)^2
+    const double ph = h * h;
+    const double pl = fma(h, h, -ph) + 2.0 * (h * l);
+    h = ph + pl;
+    l = pl - (h - ph);
+  }
+  const int ik = (int)k;
+  hi = ldexp(h, ik);
+  lo = ldexp(l, ik);
+}
+
 // what one observed point contributes
 struct LikPoint {
   double logp;   // log p without its f-independent normaliser
@@ -47,10 +96,13 @@ struct LikPoint {
 // KIND 0: Poisson, rate e exp(f).  KIND 1: binomial, y of e trials, logit link.
 // b = f + g / w is formed from y / w and the closed form of the rest (-1, or
 // -1 / sigmoid(-f)), not from the quotient of two rounded values.  Binomial, f
-// >= 0: 1 / sigmoid(-f) = 1 + exp(f) dwarfs f, and where y = 0 it is all of b;
-// it is taken as 1 + (r + r_lo), r + r_lo = 1 / exp(-f) to twice the working
-// precision, and joined to the rest by an exact two-term sum, so b carries the
-// error of exp and one rounding.
+// >= 0: 1 / sigmoid(-f) = 1 + exp(f) dwarfs f, and where y = 0 it is all of b,
+// with 1e-14 (f + 1) as its error budget -- less than half the spacing of the
+// doubles at b from f = 36 on, so b has to be the correctly rounded value
+// there.  It is taken as 1 + (r + r_lo), r + r_lo = exp(f) to 2^-64 (exp_dd: a
+// reciprocal of the rounded exp(-f) would carry that exp's ulp, a whole
+// spacing of b), and joined to the rest by an exact two-term sum, so b carries
+// one rounding.
 template <int KIND, bool WRITE>
 __device__ __forceinline__ LikPoint lik_point(double y, double e, bool has_aux, double f) {
   LikPoint o;
@@ -58,8 +110,9 @@ __device__ __forceinline__ LikPoint lik_point(double y, double e, bool has_aux, 
   const double fc = fmin(fmax(f, -kLikClamp), kLikClamp);
   if (KIND == 0) {
     const double ec = exp(fc);
-    // the rate at the unclamped f (one exp serves both)
-    const double ex = f > kLikClamp ? HUGE_VAL : (f < -kLikClamp ? 0.0 : ec);
+    // the rate at the unclamped f: one exp serves both within the clamp; beyond
+    // it exp(f) itself (finite up to f = 709.78, then inf; denormal, then 0)
+    const double ex = fabs(f) > kLikClamp ? exp(f) : ec;
     const double rate = e * ex;
     o.g = y - rate;
     o.logp = fma(y, f, -rate);
@@ -83,12 +136,9 @@ __device__ __forceinline__ LikPoint lik_point(double y, double e, bool has_aux, 
     if (WRITE) {
       const double den = 1.0 + t;
       o.noise = (den * den) / (e * t);              // 1 / (e sigmoid(f) sigmoid(-f))
-      // b = (y / w + f - 1) - r - r_lo, r + r_lo = 1 / t (f >= 0) or t
+      // b = (y / w + f - 1) - r - r_lo, r + r_lo = exp(|fc|) (f >= 0) or t
       double r = t, r_lo = 0.0;
-      if (f >= 0.0) {
-        r = 1.0 / t;
-        r_lo = r * fma(-r, t, 1.0);
-      }
+      if (f >= 0.0) exp_dd(afc, r, r_lo);
       const double s = fma(y, o.noise, f - 1.0);
       const double hi = s - r;                       // two-sum: hi + lo = s - r
       const double bb = hi - s;

@@ -1225,6 +1225,12 @@ class GPGridLaplaceModel(GPGridModel):
     (likelihood='binomial', trials= t, default 1: Bernoulli).  y need not be
     integer (fractional pseudo-counts are legitimate).  mask as GPGridModel:
     Y, exposure and trials at the missing points are ignored (NaN allowed).
+    exposure and trials are meant to lie within [1e-4, 1e4] at the observed
+    points: that is the range over which gg_lik_newton keeps the Newton step's
+    noise 1 / w finite and positive for every f (include/gp_grief_amd.h).
+    Positive finite values outside it are accepted with a logged warning --
+    rescale the exposure's unit, which only moves the latent mean by a
+    constant.
 
     fit() finds the mode a^ of psi(a) = sum_o log p(y_i | (K a)_i) - 1/2 a^T K a
     by linalg.LaplaceNewton (newton_tol, max_newton; the weighted masked CG to
@@ -1288,6 +1294,11 @@ class GPGridLaplaceModel(GPGridModel):
             if not np.all(np.isfinite(ah[m]) & (ah[m] > 0)):
                 raise ValueError("%s must be positive and finite at every observed point" %
                                  ('exposure' if likelihood == 'poisson' else 'trials'))
+            if ah[m].min() < 1e-4 or ah[m].max() > 1e4:
+                logger.warning('%s spans [%g, %g], outside [1e-4, 1e4]: the Newton step\'s noise '
+                               '1 / w may overflow or vanish at extreme f; rescale its unit'
+                               % ('exposure' if likelihood == 'poisson' else 'trials',
+                                  ah[m].min(), ah[m].max()))
         if not np.all(np.isfinite(yh[m]) & (yh[m] >= 0)):
             raise ValueError("Y must be non-negative and finite at every observed point")
         if likelihood == 'binomial' and np.any(yh[m] > (1.0 if ah is None else ah[m])):

@@ -619,12 +619,24 @@ int gg_sample_accumulate(const double* f_dev, const double* w_dev, double* out_d
  * y log e - lgamma(y + 1); binomial: lgamma(t + 1) - lgamma(y + 1) - lgamma(t
  * - y + 1)).  The caller adds the sum of the normalisers over the observed
  * points, a per-model constant, to sums[0]; no lgamma runs on the device.
- * exp is only ever taken of a clamped or non-positive argument (binomial:
- * exp(-|f|), log1p(exp(-|f|))).  For |f| <= 700 the noise 1 / w is finite and
- * positive (aux within [1e-4, 1e4]); beyond, f is clamped to +-700 where w
+ * The binomial only ever takes exp of a non-positive argument (exp(-|f|),
+ * log1p(exp(-|f|))).  With aux within [1e-4, 1e4] the noise 1 / w is finite
+ * and positive for every f: beyond |f| = 700, f is clamped to +-700 where w
  * and its derived outputs (noise_out, log w, the g / w term of b_out) are
- * formed, and only there: g and log p use f as given (a Poisson rate may then
- * overflow to inf, which the caller's line search rejects).                  */
+ * formed, and only there.  At the Poisson corners (e = 1e-4, f <= -700: noise
+ * 1.014e308; e = 1e4, f >= 700: noise 9.86e-309, a denormal number) that holds
+ * by a hair, and outside that range of aux it does not.  g and log p use f as
+ * given: the Poisson rate is e exp(f) at the unclamped f, finite up to f =
+ * 709.78 and inf beyond, where sums[0] = -inf and sums[3] = sums[4] = +inf
+ * (sums[1] and sums[2] stay finite, nothing is NaN) -- the caller's line search
+ * rejects such a trial; the binomial takes exp(-|f|) as 0 beyond the clamp
+ * and its sums are finite for every finite f.  b_out is finite while y / w is:
+ * for the Poisson y / w = y / (e exp(f)) overflows to +inf inside the range
+ * above once y > 1.77e308 e exp(f) (e = 1e-4, f = -700: y >= 2).  b_out has
+ * been measured within 1e-14 (|f| + (|y| + w) / w) of a long-double evaluation;
+ * for the binomial with y = 0 and f >= 36, where that is less than half the
+ * spacing of the doubles at b = f - 1 - exp(f), this asks for the correctly
+ * rounded value, and exp(f) is formed to 2^-64 there to give it.             */
 #define GG_LIK_POISSON 0
 #define GG_LIK_BINOMIAL 1
 /* One fused streaming pass over n points.  Reads y, aux (NULL = 1), f, a and

@@ -29,13 +29,14 @@ CASES = [((7, 5, 3), 0.2, 1.0), ((12, 10, 8), 0.1, 1.0), ((12, 10, 8), 0.0, 2.0)
 LIKELIHOODS = ["poisson", "binomial"]
 
 
-def factors(ms, amp=1.0):
-    """masked_ref.rbf_factors with the variance amp^2 on factor 0."""
+def factors(ms, amp=1.0, ls=0.1):
+    """masked_ref.rbf_factors (lengthscales ls (1 + 0.05 i)) with the variance
+    amp^2 on factor 0."""
     F = []
     for i, m in enumerate(ms):
         g = np.linspace(0, 1, m)
         var = float(amp) ** 2 if i == 0 else 1.0
-        F.append(oracle.cov_1d("RBF", g, g, var, 0.1 * (1 + 0.05 * i)) + 1e-12 * np.eye(m))
+        F.append(oracle.cov_1d("RBF", g, g, var, ls * (1 + 0.05 * i)) + 1e-12 * np.eye(m))
     return F
 
 
@@ -124,7 +125,9 @@ def newton(F, kind, y, aux, mask, solve="cg", cg_rtol=1e-11, newton_tol=1e-8, ma
     a|^2, which psi (a sum with terms up to 1e5 here) no longer resolves once
     the residual is near 1e-6; judged by psi alone it would be refused one
     step short of the tolerance.  solve: 'cg' (noise_ref.weighted_cg to cg_rtol, x0
-    = 0) or 'dense'."""
+    = 0) or 'dense'.  precond='kron': the preconditioner's scalar stand-in for
+    the noise is the geometric mean of the noise at a = 0 on every step and
+    whatever a0 is, as the device's solver fixes it when it is built."""
     mask = np.asarray(mask, dtype=bool).reshape(-1)
     n = mask.size
     const = log_norm(kind, y, aux, mask)
@@ -134,6 +137,10 @@ def newton(F, kind, y, aux, mask, solve="cg", cg_rtol=1e-11, newton_tol=1e-8, ma
     psi = sums[0] + const - 0.5 * sums[1]
     out = dict(iters=0, converged=False, stalled=False, cg_iters=[], psis=[psi], halvings=[])
     small_gain = False
+    shift = None
+    if precond == "kron":
+        zero = np.zeros(n)
+        shift = nr.geometric_mean(mask, newton_pass(kind, y, aux, zero, zero, mask)[0])
     while True:
         if _stop(sums, newton_tol):
             out["converged"] = True
@@ -144,7 +151,8 @@ def newton(F, kind, y, aux, mask, solve="cg", cg_rtol=1e-11, newton_tol=1e-8, ma
         if solve == "dense":
             a_full = nr.dense_solve(F, b, mask, noise)
         else:
-            a_full, _, it = nr.weighted_cg(F, b, mask, noise, rtol=cg_rtol, precond=precond)
+            a_full, _, it = nr.weighted_cg(F, b, mask, noise, rtol=cg_rtol, precond=precond,
+                                          shift=shift)
             out["cg_iters"].append(it)
         d = a_full - a
         s, accepted = 1.0, False
