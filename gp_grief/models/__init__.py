@@ -3,7 +3,7 @@ import sys as _sys
 
 from gp_grief_amd.models import (BaseModel, GPRegressionModel, GPGriefModel,  # noqa: F401
                                  GPwebModel, GPwebTransformedModel, GPGridModel,
-                                 GPGridLaplaceModel)
+                                 GPGridLaplaceModel, GPSKIModel)
 from .._alias import register as _register
 
 _register(_sys.modules[__name__], {

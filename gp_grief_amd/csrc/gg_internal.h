@@ -322,7 +322,15 @@ __global__ void lz_coef_kernel(double* __restrict__ lzs, const double* __restric
 __global__ void lz_beta_kernel(double* __restrict__ lzs, double* __restrict__ beta);
 
 // ---- the single-GPU CG's kernels (gg_vec.hip) that the sharded CG's scalars
-// (gg_cgs.hip) launch too
+// (gg_cgs.hip) launch too; the textbook recurrence's scalar kernels also serve
+// the CG on scattered points (gg_ski.hip)
+__global__ void cg_init_kernel(const double* __restrict__ partials, int64_t count,
+                               CgScalars* sc, double rtol, double atol);
+__global__ __launch_bounds__(1024) void cg_alpha_kernel(const double* __restrict__ partials,
+                                                        int64_t count, CgScalars* sc);
+__global__ __launch_bounds__(1024) void cg_rho_kernel(const double* __restrict__ partials,
+                                                      int64_t count, CgScalars* sc,
+                                                      int need_pending);
 __global__ __launch_bounds__(kVecThreads) void cg_xr_update_kernel(
     double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
     const double* __restrict__ q, int64_t n, const CgScalars* __restrict__ sc,

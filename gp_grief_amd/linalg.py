@@ -448,9 +448,282 @@ class MaskedKronCG(object):
             pass
 
 
+def _even_axis(g, order, f):
+    """(lo, h, m) of grid axis f, refused unless evenly spaced to 1e-9 h."""
+    a = np.asarray(g, dtype=np.float64).reshape(-1)
+    m = int(a.size)
+    if m < order:
+        raise ValueError("grid axis %d has %d nodes, %s interpolation needs %d"
+                         % (f, m, 'cubic' if order == 4 else 'linear', order))
+    h = (a[-1] - a[0]) / (m - 1)
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError("grid axis %d must be increasing and finite" % f)
+    if np.max(np.abs(a - (a[0] + h * np.arange(m)))) > 1e-9 * h:
+        raise ValueError("grid axis %d is not evenly spaced (structured kernel interpolation "
+                         "needs evenly spaced axes)" % f)
+    return float(a[0]), float(h), m
+
+
+class GridInterp(object):
+    """The sparse interpolation operator W (n x N) of structured kernel
+    interpolation (KISS-GP, Wilson & Nickisch 2015) between the nodes of the
+    grid xg (a list of d evenly spaced axes, input dimension 0 fastest like Y
+    and mask of GPGridModel) and n scattered points X (n, d; numpy or device):
+    cov(X, X) is approximated by W K W^T, K the grid operator.  order 'cubic'
+    (Keys' cubic convolution, 4^d nodes per point, d <= 4) or 'linear' (2^d
+    nodes, d <= 8).
+
+    Every point must lie inside the interpolation domain -- for 'cubic' one
+    cell inside the grid's ends on every axis (1 <= (x - lo) / h <= m - 2), for
+    'linear' between the ends.  There is no clamping and no extrapolation: a
+    point outside raises ValueError with the count.  Pad the grid by one cell
+    around the data (InducingGrid(beyond_domain=) does that).
+
+    interp(g): W g, grid -> points.  spread(p): W^T p, points -> grid, without
+    atomics through an inverted index built here once (bitwise reproducible).
+    n, N, nnz: points, nodes, entries of W.  Holds the stencil tables, the
+    index and the library handle (gg_ski_*)."""
+
+    SPLIT = 512   # rows of the inverted index longer than this are summed in chunks
+
+    def __init__(self, xg, X, order='cubic'):
+        from . import device as dev
+        from . import native
+        if order not in ('cubic', 'linear'):
+            raise ValueError("order must be 'cubic' or 'linear'")
+        self.order = order
+        o = 4 if order == 'cubic' else 2
+        d = len(xg)
+        if o ** d > 256:
+            raise ValueError("%s interpolation supports d <= %d (order^d <= 256), not d = %d"
+                             % (order, 4 if o == 4 else 8, d))
+        axes = [_even_axis(g, o, f) for f, g in enumerate(xg)]
+        t = dev.torch()
+        if isinstance(X, t.Tensor):
+            if X.dim() != 2 or X.shape[1] != d:
+                raise ValueError("X must be (n, %d)" % d)
+            Xd = dev.to_device(X)
+        else:
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim != 2 or X.shape[1] != d:
+                raise ValueError("X must be (n, %d)" % d)
+            Xd = dev.to_device(X)
+        n = int(Xd.numel()) // d
+        if n < 1:
+            raise ValueError("X holds no point")
+        self.d, self.n = d, n
+        self.m = [a[2] for a in axes]
+        self.N = int(np.prod(self.m))
+        S = o ** d
+        self.nnz = n * S
+        L = native.lib()
+        ms = native.i64_array(self.m)
+        lo = (ctypes.c_double * d)(*[a[0] for a in axes])
+        h = (ctypes.c_double * d)(*[a[1] for a in axes])
+        device = dev.device()
+        self.first = t.empty(n * d, dtype=t.int32, device=device)
+        self.w = dev.empty(n * d * o)
+        out = ctypes.c_int64()
+        native.check(L.gg_ski_stencils(d, ms, lo, h, o, native.dptr(Xd), n,
+                                       ctypes.c_void_p(self.first.data_ptr()),
+                                       native.dptr(self.w), ctypes.byref(out),
+                                       native.stream_ptr()), "gg_ski_stencils")
+        # the inverted index of W^T: the entries sorted stably by node (within
+        # a node in point order), an int64 row pointer
+        node = t.empty(self.nnz, dtype=t.int64, device=device)
+        wprod = dev.empty(self.nnz)
+        native.check(L.gg_ski_expand(d, ms, o, n, ctypes.c_void_p(self.first.data_ptr()),
+                                     native.dptr(self.w), ctypes.c_void_p(node.data_ptr()),
+                                     native.dptr(wprod), native.stream_ptr()), "gg_ski_expand")
+        node, perm = t.sort(node, stable=True)
+        self.point = t.div(perm, S, rounding_mode='floor').to(t.int32)
+        self.wprod = wprod[perm]
+        del wprod, perm
+        self.rowptr = t.searchsorted(node, t.arange(self.N + 1, dtype=t.int64, device=device))
+        del node
+        lens = self.rowptr[1:] - self.rowptr[:-1]
+        self.max_row = int(lens.max().item())
+        long_node = t.nonzero(lens > self.SPLIT).reshape(-1)
+        nlong = int(long_node.numel())
+        nchunks = 0
+        self._long = None
+        ptrs = [None] * 5
+        if nlong:
+            per = (lens[long_node] + self.SPLIT - 1) // self.SPLIT
+            coff = t.zeros(nlong + 1, dtype=t.int64, device=device)
+            coff[1:] = t.cumsum(per, 0)
+            nchunks = int(coff[-1].item())
+            row = t.repeat_interleave(t.arange(nlong, dtype=t.int64, device=device), per)
+            k = t.arange(nchunks, dtype=t.int64, device=device) - coff[row]
+            cb = self.rowptr[long_node[row]] + k * self.SPLIT
+            ce = t.minimum(cb + self.SPLIT, self.rowptr[long_node[row] + 1])
+            csum = dev.empty(nchunks)
+            self._long = (long_node.contiguous(), coff, cb.contiguous(), ce.contiguous(), csum)
+            ptrs = [ctypes.c_void_p(a.data_ptr()) for a in self._long]
+        self.long_rows, self.chunks = nlong, nchunks
+        hd = ctypes.c_void_p()
+        native.check(L.gg_ski_create(d, ms, o, n, ctypes.c_void_p(self.first.data_ptr()),
+                                     native.dptr(self.w), ctypes.c_void_p(self.rowptr.data_ptr()),
+                                     ctypes.c_void_p(self.point.data_ptr()),
+                                     native.dptr(self.wprod), self.SPLIT, nlong, ptrs[0], ptrs[1],
+                                     nchunks, ptrs[2], ptrs[3], ptrs[4], ctypes.byref(hd)),
+                     "gg_ski_create")
+        self.h = hd
+
+    def _apply(self, fn, v, n_in, n_out, out, what):
+        from . import device as dev
+        from . import native
+        was_dev = dev.is_device_array(v)
+        vd = v.detach().reshape(-1) if _is_device_doubles(v) else dev.to_device(v)
+        if vd.numel() != n_in:
+            raise ValueError("%s: the input must have %d entries, not %d"
+                             % (what, n_in, vd.numel()))
+        if out is None:
+            od = dev.empty(n_out)
+        else:
+            if not _is_device_doubles(out) or out.numel() != n_out:
+                raise ValueError("%s: out must be a contiguous float64 device tensor of %d "
+                                 "entries" % (what, n_out))
+            if out.data_ptr() == vd.data_ptr():
+                raise ValueError("%s: out must not be the input" % what)
+            od = out
+        native.check(fn(self.h, native.dptr(vd), native.dptr(od), native.stream_ptr()), what)
+        if out is not None or was_dev:
+            return od
+        return dev.to_host(od).reshape((n_out,) + np.shape(v)[1:])
+
+    def interp(self, g, out=None):
+        """W g: the N grid values interpolated to the n points (numpy in, numpy
+        out; device in or out=, the device tensor)."""
+        from . import native
+        return self._apply(native.lib().gg_ski_interp, g, self.N, self.n, out, "gg_ski_interp")
+
+    def spread(self, p, out=None):
+        """W^T p: the n point values spread onto the N nodes; nodes that no
+        point touches get exactly 0."""
+        from . import native
+        return self._apply(native.lib().gg_ski_spread, p, self.n, self.N, out, "gg_ski_spread")
+
+    def __del__(self):
+        try:
+            from . import native
+            if getattr(self, "h", None) is not None and self.h.value:
+                native.load().gg_ski_destroy(self.h)
+        except Exception:
+            pass
+
+
+class SKICG(object):
+    """Resident CG state for (W K W^T + shift I) x = b over the n scattered
+    points of a GridInterp W (gg_skicg_*): structured kernel interpolation on
+    the Kronecker operator K.  Grid basis, textbook recurrence, x0 = 0; start /
+    iterate / status / solve as MaskedKronCG.  coefficients() returns the
+    (alpha_j, beta_j) of the current solve's iterations (at most max_steps are
+    kept), from which tridiag() rebuilds the Lanczos tridiagonal."""
+
+    def __init__(self, K, W, shift, max_steps=1024):
+        from . import device as dev
+        from . import native
+        if not isinstance(W, GridInterp):
+            raise ValueError("W must be a GridInterp")
+        if int(K.shape[0]) != W.N or int(K.shape[1]) != W.N:
+            raise ValueError("K must be %d x %d, the grid of W" % (W.N, W.N))
+        self.K, self.W = K, W
+        self.n = W.n
+        self.shift = float(shift)
+        self.max_steps = int(max_steps)
+        self._dk = K._device()
+        L = native.lib()
+        we = ctypes.c_int64()
+        native.check(L.gg_skicg_work_elems(self._dk.h, W.h, ctypes.byref(we)),
+                     "gg_skicg_work_elems")
+        self.work = dev.empty(we.value)
+        h = ctypes.c_void_p()
+        native.check(L.gg_skicg_create(self._dk.h, W.h, self.shift, native.dptr(self.work),
+                                       self.max_steps, ctypes.byref(h)), "gg_skicg_create")
+        self.h = h
+        self.x = None
+
+    def start(self, b_dev, rtol=1e-5, atol=0.0, x_out=None):
+        from . import device as dev
+        from . import native
+        if b_dev.numel() != self.n:
+            raise ValueError("b must have %d entries" % self.n)
+        self.b = b_dev.reshape(-1)
+        self.x = dev.empty(self.n) if x_out is None else x_out
+        native.check(native.lib().gg_skicg_start(self.h, native.dptr(self.b),
+                                                 native.dptr(self.x), float(rtol), float(atol),
+                                                 native.stream_ptr()), "gg_skicg_start")
+
+    def iterate(self, n_iter, check_every=0):
+        from . import native
+        n_iter = min(int(n_iter), 2 ** 31 - 1)
+        native.check(native.lib().gg_skicg_iterate(self.h, n_iter, min(int(check_every), n_iter),
+                                                   native.stream_ptr()), "gg_skicg_iterate")
+
+    def status(self):
+        from . import native
+        it, conv = ctypes.c_int(), ctypes.c_int()
+        res, tol = ctypes.c_double(), ctypes.c_double()
+        native.check(native.lib().gg_skicg_status(self.h, ctypes.byref(it), ctypes.byref(conv),
+                                                  ctypes.byref(res), ctypes.byref(tol),
+                                                  native.stream_ptr()), "gg_skicg_status")
+        return it.value, bool(conv.value), res.value, tol.value
+
+    def solve(self, b_dev, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, x_out=None):
+        """start + iterate to convergence: (x, iterations, converged, |r|, tol)."""
+        if maxiter is None:
+            maxiter = self.n * 10
+        if check_every is None:
+            check_every = 10 if max(self.n, self.W.N) >= 1 << 20 else 50
+        self.start(b_dev, rtol, atol, x_out=x_out)
+        self.iterate(maxiter, check_every=check_every)
+        return (self.x,) + self.status()
+
+    def coefficients(self):
+        """(alphas, betas) of the current solve's iterations, numpy."""
+        from . import native
+        k = self.max_steps
+        a = (ctypes.c_double * max(k, 1))()
+        b = (ctypes.c_double * max(k, 1))()
+        got = ctypes.c_int()
+        native.check(native.lib().gg_skicg_coefficients(self.h, k, a, b, ctypes.byref(got),
+                                                        native.stream_ptr()),
+                     "gg_skicg_coefficients")
+        return np.array(a[:got.value]), np.array(b[:got.value])
+
+    def __del__(self):
+        try:
+            from . import native
+            if getattr(self, "h", None) is not None and self.h.value:
+                native.load().gg_skicg_destroy(self.h)
+        except Exception:
+            pass
+
+
+def cg_tridiag(alphas, betas):
+    """The Lanczos tridiagonal of the Krylov space a CG run spanned, from its
+    coefficients: T_jj = 1 / alpha_j + beta_{j-1} / alpha_{j-1}, T_{j,j+1} =
+    sqrt(beta_j) / alpha_j.  (diagonal, off-diagonal), host."""
+    a = np.asarray(alphas, dtype=np.float64)
+    b = np.asarray(betas, dtype=np.float64)
+    k = a.size
+    diag = 1.0 / a
+    diag[1:] += b[:k - 1] / a[:k - 1]
+    return diag, np.sqrt(b[:k - 1]) / a[:k - 1]
+
+
+def _refuse_with_interp(**given):
+    for name, v in given.items():
+        if v is not None:
+            raise ValueError("interp=: the CG on scattered points runs on one GPU in the grid "
+                             "basis without a mask, per-point noise or a preconditioner; %s= "
+                             "cannot be combined" % name)
+
+
 def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, callback=None,
        recurrence=None, fusion=None, basis=None, comm=None, decomposition="auto",
-       mask=None, precond=None, noise=None):
+       mask=None, precond=None, noise=None, interp=None):
     """Solve (K + shift I) x = b with CG on the device (x0 = 0).
 
     Same stopping rule and iterates as scipy.sparse.linalg.cg (recurrence:
@@ -483,8 +756,31 @@ def cg(K, b, shift=0.0, rtol=1e-5, atol=0.0, maxiter=None, check_every=None, cal
     has one source of truth: shift must be 0 (or omitted) with noise=.  The
     rules of mask= hold (no comm=, basis='block', recurrence='fused' or
     fusion); precond='kron' is allowed.
+
+    interp (a GridInterp W over K's grid): scattered data by structured kernel
+    interpolation -- CG on (W K W^T + shift I) x = b over W.n points (SKICG); b
+    and x have W.n entries.  Cannot be combined with mask=, noise=, comm=,
+    basis= or precond= (ValueError).
     """
     from . import device as dev
+    if interp is not None:
+        _refuse_with_interp(mask=mask, noise=noise, comm=comm, basis=basis, precond=precond,
+                            recurrence=None if recurrence == "textbook" else recurrence,
+                            fusion=fusion)
+        was_dev = dev.is_device_array(b)
+        bd = dev.to_device(b)
+        if bd.numel() != interp.n:
+            raise ValueError('b is the wrong shape, must have %d entries' % interp.n)
+        solver = SKICG(K, interp, shift, max_steps=0)
+        x, it, conv, res, tol = solver.solve(bd, rtol, atol, maxiter=maxiter,
+                                             check_every=check_every)
+        if callback is not None:
+            for _ in range(it):
+                callback()
+        info = 0 if conv else it
+        out = x.reshape(tuple(b.shape)) if was_dev else dev.to_host(x).reshape(np.shape(b))
+        cg.last = CGResult(out, info, it, res, tol)
+        return out, info
     n = int(K.shape[0])
     if precond is not None and mask is None and noise is None:
         raise ValueError("precond= needs mask= (on a complete grid solve_schur is exact)")
@@ -690,7 +986,34 @@ def _mask_device_bytes(mask, n):
     return _mask_to_device(mask, n)[0]
 
 
-def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None, noise=None):
+def _slq_logdet_interp(K, shift, probes, steps, seed, W):
+    """SLQ for log det(W K W^T + shift I): per probe z = gg_probe_fill(seed,
+    probe) of length n, `steps` CG iterations with rtol = atol = 0, T from the
+    coefficients, n e_1^T log(T) e_1."""
+    from . import device as dev
+    from . import native
+    n = W.n
+    steps = max(1, min(int(steps), n))
+    solver = SKICG(K, W, shift, max_steps=steps)
+    z, x = dev.empty(n), dev.empty(n)
+    ests = []
+    for j in range(probes):
+        native.check(native.lib().gg_probe_fill(int(seed), j, native.dptr(z), n,
+                                                native.stream_ptr()), "gg_probe_fill")
+        solver.start(z, 0.0, 0.0, x_out=x)
+        solver.iterate(steps)
+        a, b = solver.coefficients()
+        # an exactly invariant Krylov space ends the recurrence early (rho = 0)
+        ok = np.isfinite(a) & np.isfinite(b) & (a > 0)
+        k = int(a.size if ok.all() else np.argmin(ok))
+        diag, off = cg_tridiag(a[:k], b[:k])
+        T = np.diag(diag) + np.diag(off, 1) + np.diag(off, -1)
+        theta, U = np.linalg.eigh(T)
+        ests.append(float(n) * float(np.sum(U[0, :] ** 2 * np.log(theta))))
+    return float(np.mean(ests)), np.array(ests)
+
+
+def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None, noise=None, interp=None):
     """Stochastic Lanczos quadrature estimate of log det(K + shift I):
     (mean, per-probe estimates).
 
@@ -700,7 +1023,15 @@ def slq_logdet(K, shift, probes=8, steps=30, seed=0, mask=None, noise=None):
     whatever the number of missing points.
 
     noise (as lanczos_tridiag; checked once here): the estimate of
-    log det(K_oo + D_oo), D = diag(noise); shift must be 0."""
+    log det(K_oo + D_oo), D = diag(noise); shift must be 0.
+
+    interp (a GridInterp W): the estimate of log det(W K W^T + shift I) over the
+    W.n scattered points, from `steps` iterations of the CG on the points per
+    probe (SKICG with rtol = atol = 0) whose coefficients give the Lanczos
+    tridiagonal (cg_tridiag); cannot be combined with mask= or noise=."""
+    if interp is not None:
+        _refuse_with_interp(mask=mask, noise=noise)
+        return _slq_logdet_interp(K, shift, probes, steps, seed, interp)
     n = int(K.shape[0])
     scale, kw = n, {}
     if noise is not None and mask is None:

@@ -25,6 +25,10 @@
                  CG (linalg.LaplaceNewton), Laplace LML with the weighted SLQ
                  log det, GPGridModel's posterior machinery on the
                  pseudo-targets, response-scale moments.
+  GPSKIModel     (new) scattered data by structured kernel interpolation: the
+                 covariance W K W^T of linalg.GridInterp on the Kronecker
+                 operator, CG on the points (linalg.SKICG), SLQ log det from
+                 the CG's coefficients or an exact dense one for small n.
 
 Device state keeps the reference's attribute names (_Phi, _A, _P, _Pchol,
 _alpha, _alpha_p) holding CUDA tensors (or small host arrays where the
@@ -1393,6 +1397,188 @@ class GPGridLaplaceModel(GPGridModel):
                 native.dptr(m2), k + 1, n, native.stream_ptr()), "gg_lik_response_accumulate")
         m2 /= S - 1
         return self._out(mean), self._out(m2)
+
+
+class GPSKIModel(BaseModel):
+    """Gaussian process on n scattered points X (n, d) by structured kernel
+    interpolation (KISS-GP, Wilson & Nickisch 2015): cov(X, X) is approximated
+    by W K W^T, K = kern.cov_grid(xg) the Kronecker operator on the grid xg
+    (evenly spaced axes) and W the sparse interpolation matrix of
+    linalg.GridInterp (interp 'cubic' or 'linear').  Unlike GPGridModel(mask=)
+    the data need not sit on the nodes, and a cell may hold many points.
+
+    Every point must lie inside the interpolation domain -- for 'cubic' one
+    cell inside the grid's ends on every axis -- or ValueError is raised with
+    the count: pad the grid by one cell around the data
+    (InducingGrid(beyond_domain=) does that).
+
+    fit(): alpha = (W K W^T + s I)^-1 y by the CG on the points (linalg.SKICG,
+    cached on (kernel parameters, noise); cg_iters keeps the iteration count).
+    LML = -1/2 (y^T alpha + log det(W K W^T + s I) + n log 2 pi) with logdet
+      'slq'    stochastic Lanczos quadrature from the same CG driver
+               (linalg.slq_logdet(interp=); slq_probes, slq_steps, seed; the
+               per-probe estimates stay in slq_estimates, the seed is fixed, so
+               the objective is deterministic), or
+      'exact'  the n x n matrix formed by n unit-vector applications and the
+               device Cholesky, for n <= exact_max (a cost guard, not a tuned
+               value); alpha then comes from that same factor, not from CG.
+    The gradient is BaseModel's finite differences; the stencils and the index
+    depend on X and the grid only and are built once.  predict_grid(): the
+    latent mean K W^T alpha on all N nodes.  predict(Xnew): mean K(X*, grid)
+    W^T alpha through the exact cross-covariance to the nodes (the Khatri-Rao
+    path), variance k** - k*^T (W K W^T + s I)^-1 k* + s with k* = W (Kronecker
+    row of x*), one solve per test row."""
+
+    def __init__(self, X, Y, kern, xg, noise_var=1., interp='cubic', logdet='slq',
+                 cg_rtol=1e-10, slq_probes=8, slq_steps=50, seed=0, exact_max=4096,
+                 dim_noise_var=1e-12):
+        super(GPSKIModel, self).__init__()
+        from .kern import GridKernel
+        from .linalg import GridInterp
+        assert isinstance(kern, GridKernel)
+        if logdet not in ('slq', 'exact'):
+            raise ValueError("logdet must be 'slq' or 'exact'")
+        self.xg = xg
+        self.kern = kern
+        self.W = GridInterp(xg, X, order=interp)
+        self.num_data = self.W.n
+        self.num_grid = self.W.N
+        if tuple(Y.shape) != (self.num_data, 1):
+            raise ValueError('Y must be (%d,1), one row per point of X' % self.num_data)
+        if logdet == 'exact' and self.num_data > int(exact_max):
+            raise ValueError("logdet='exact' needs %d operator applications and a %d x %d "
+                             "Cholesky, above exact_max=%d; raise it or use logdet='slq'"
+                             % (self.num_data, self.num_data, self.num_data, int(exact_max)))
+        self._y_is_dev = dev.is_device_array(Y)
+        self._yd = dev.to_device(Y)
+        self.noise_var = np.float64(noise_var)
+        self.logdet = logdet
+        self.dim_noise_var = float(dim_noise_var)
+        self.cg_rtol = float(cg_rtol)
+        self.slq = (int(slq_probes), int(slq_steps), int(seed))
+        self.slq_estimates = None
+        self.exact_max = int(exact_max)
+        self.cg_iters = None
+        self.grad_method = 'finite_difference'
+        self._K = self._kern_key = None
+        self._scg = self._scg_key = None
+        self._chol = self._chol_key = None
+        self.dependent_attributes = list(self.dependent_attributes)
+        self._alpha = self._log_like = self._gradient = self._log_det = None
+
+    def _operator(self):
+        key = np.asarray(self.kern.parameters).copy()
+        if self._K is None or not np.array_equal(key, self._kern_key):
+            self._K = self.kern.cov_grid(self.xg, dim_noise_var=self.dim_noise_var)
+            self._kern_key = key
+        return self._K
+
+    def _solver_key(self):
+        """The values the system W K W^T + s I depends on (not id(K): the
+        operator is dropped on every parameter change and its id may be handed
+        to the next one)."""
+        return (tuple(float(v) for v in np.ravel(self.kern.parameters)), float(self.noise_var))
+
+    def _ski_cg(self):
+        """The resident solver, cached on (kernel parameters, noise)."""
+        from .linalg import SKICG
+        K = self._operator()
+        key = self._solver_key()
+        if self._scg is None or self._scg_key != key:
+            self._scg = SKICG(K, self.W, float(self.noise_var), max_steps=0)
+            self._scg_key = key
+        return self._scg
+
+    def _apply_wkw(self, v, out=None):
+        """W K W^T v on the device."""
+        return self.W.interp(self._operator().matvec_device(self.W.spread(v)), out=out)
+
+    def _factor(self):
+        """Cholesky of the dense W K W^T + s I (logdet='exact'), cached like the
+        solver: n unit-vector applications."""
+        K = self._operator()
+        key = self._solver_key()
+        if self._chol is None or self._chol_key != key:
+            t = dev.torch()
+            n = self.num_data
+            A = t.empty((n, n), dtype=t.float64, device=self._yd.device)
+            e = dev.zeros(n)
+            for i in range(n):
+                e[i] = 1.0
+                self._apply_wkw(e, out=A[i])
+                e[i] = 0.0
+            A = 0.5 * (A + A.T)
+            self._chol = dense.Cholesky(dense.add_diag(A, float(self.noise_var)))
+            self._chol_key = key
+        return self._chol
+
+    def _solve(self, b):
+        """(W K W^T + s I)^-1 b for a device vector b."""
+        if self.logdet == 'exact':
+            return self._factor().solve(b)
+        x, it, conv, res, tol = self._ski_cg().solve(b, rtol=self.cg_rtol)
+        if not conv:
+            logger.info('SKI CG did not converge in %d iterations' % it)
+        self._last_iters = it
+        return x.clone()
+
+    def fit(self):
+        self.parameters
+        if self._alpha is not None:
+            return
+        self._alpha = self._solve(self._yd)
+        if self.logdet != 'exact':
+            self.cg_iters = self._last_iters
+
+    def _cov_log_det(self):
+        if self._log_det is None:
+            if self.logdet == 'exact':
+                self._log_det = self._factor().logdet
+            else:
+                from .linalg import slq_logdet
+                probes, steps, seed = self.slq
+                self._log_det, self.slq_estimates = slq_logdet(
+                    self._operator(), float(self.noise_var), probes=probes, steps=steps,
+                    seed=seed, interp=self.W)
+        return self._log_det
+
+    def _compute_log_likelihood(self, parameters):
+        self.parameters = parameters
+        self.fit()
+        ll = -0.5 * (dense.dot(self._yd, self._alpha) + self._cov_log_det()
+                     + self.num_data * np.log(2 * np.pi))
+        return np.array([[ll]])
+
+    def _out(self, vd):
+        return vd.reshape(-1, 1) if self._y_is_dev else dev.to_host(vd).reshape(-1, 1)
+
+    def predict_grid(self):
+        """The latent posterior mean K W^T alpha on all N grid nodes, (N, 1)."""
+        self.fit()
+        return self._out(self._operator().matvec_device(self.W.spread(self._alpha)))
+
+    def predict(self, Xnew, compute_var=True):
+        """Posterior at Xnew (M x d): mean K(X*, grid) W^T alpha, (M, 1), and the
+        predictive variance k** - k*^T (W K W^T + s I)^-1 k* + s with k* =
+        W kron_f k_f(x*), one solve per test row."""
+        from .tensors import KronMatrix
+        assert Xnew.ndim == 2 and Xnew.shape[1] == len(self.xg)
+        self.fit()
+        Kxz = self.kern.cov_kr(np.asarray(Xnew, dtype=np.float64), self.xg)
+        mean = dense.host(Kxz.contract(self.W.spread(self._alpha))).reshape(-1, 1)
+        if not compute_var:
+            return mean, None
+        s = float(self.noise_var)
+        A = [dense.host(Af) if dev.is_device_array(Af) else np.asarray(Af) for Af in Kxz.A]
+        kss = float(self.kern.diag_val)
+        one = dev.to_device(np.ones(1))
+        var = np.empty(Xnew.shape[0])
+        for j in range(Xnew.shape[0]):
+            cols = [np.ascontiguousarray(np.asarray(Af[j, :], dtype=np.float64).reshape(-1, 1))
+                    for Af in A]
+            ks = self.W.interp(KronMatrix(cols).matvec_device(one))
+            var[j] = kss - dense.dot(ks, self._solve(ks)) + s
+        return mean, var.reshape(-1, 1)
 
 
 def _content_key(a):

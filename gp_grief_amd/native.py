@@ -120,6 +120,28 @@ SIGNATURES = {
     "gg_cgm_iterate": [_vp, ctypes.c_int, ctypes.c_int, _vp],
     "gg_cgm_status": [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp],
+    "gg_ski_stencils": [ctypes.c_int, _c_i64p, ctypes.POINTER(ctypes.c_double),
+                        ctypes.POINTER(ctypes.c_double), ctypes.c_int, _c_dp, ctypes.c_int64,
+                        _vp, _c_dp, _c_i64p, _vp],
+    "gg_ski_expand": [ctypes.c_int, _c_i64p, ctypes.c_int, ctypes.c_int64, _vp, _c_dp, _vp,
+                      _c_dp, _vp],
+    "gg_ski_create": [ctypes.c_int, _c_i64p, ctypes.c_int, ctypes.c_int64, _vp, _c_dp, _vp, _vp,
+                      _c_dp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                      _c_dp, ctypes.POINTER(ctypes.c_void_p)],
+    "gg_ski_destroy": [_vp],
+    "gg_ski_interp": [_vp, _c_dp, _c_dp, _vp],
+    "gg_ski_spread": [_vp, _c_dp, _c_dp, _vp],
+    "gg_skicg_work_elems": [_vp, _vp, _c_i64p],
+    "gg_skicg_create": [_vp, _vp, ctypes.c_double, _c_dp, ctypes.c_int,
+                        ctypes.POINTER(ctypes.c_void_p)],
+    "gg_skicg_destroy": [_vp],
+    "gg_skicg_start": [_vp, _c_dp, _c_dp, ctypes.c_double, ctypes.c_double, _vp],
+    "gg_skicg_iterate": [_vp, ctypes.c_int, ctypes.c_int, _vp],
+    "gg_skicg_status": [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp],
+    "gg_skicg_coefficients": [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                              _vp],
     "gg_lanczos_probe": [_vp, ctypes.c_double, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                          _c_dp, ctypes.POINTER(ctypes.c_double),
                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), _vp],

@@ -441,6 +441,89 @@ int gg_cgm_iterate(gg_cgm* cgm, int max_iters, int check_every, gg_stream stream
 int gg_cgm_status(gg_cgm* cgm, int* iters, int* converged, double* resid_norm, double* tol,
                   gg_stream stream); /* synchronising */
 
+/* ------------------------- structured kernel interpolation (scattered data)
+ * The covariance of n points that do not sit on the grid's nodes is W K W^T
+ * (Wilson & Nickisch 2015): K the grid operator, W the sparse n x N matrix of
+ * local interpolation weights, the tensor product of per-axis stencils of
+ * `order` nodes -- 4: Keys' cubic convolution, 2: linear; order^d <= 256.  No
+ * reference counterpart.  The grid has d evenly spaced axes,
+ * axis f with m[f] nodes lo[f] + j h[f]; input dimension 0 is fastest, the
+ * node index is sum_f j_f prod_{e<f} m[e].  With u = (x - lo) / h:
+ *   cubic   domain 1 <= u <= m - 2, m >= 4; j = min(max(floor u, 1), m - 3),
+ *           t = u - j; nodes j - 1 .. j + 2 with weights (-t^3 + 2t^2 - t) / 2,
+ *           (3t^3 - 5t^2 + 2) / 2, (-3t^3 + 4t^2 + t) / 2, (t^3 - t^2) / 2
+ *   linear  domain 0 <= u <= m - 1, m >= 2; j = min(max(floor u, 0), m - 2);
+ *           nodes j, j + 1 with weights (1 - t, t)
+ * u within 1e-10 of a domain edge counts as on it (the rounding of the
+ * division); there is no clamping beyond that and no extrapolation.
+ *
+ * gg_ski_stencils: X_dev holds n x d doubles, row-major.  Writes, per point i
+ * and axis f, the first node first_dev[i d + f] (int32) and the weights
+ * w_dev[(i d + f) order + k].  Synchronising.  *n_outside (may be NULL) gets
+ * the number of points outside the domain; if there is any, GG_ERR_VALUE (the
+ * message carries the count) and neither table is written.                   */
+int gg_ski_stencils(int d, const int64_t* m, const double* lo, const double* h, int order,
+                    const double* X_dev, int64_t n, int32_t* first_dev, double* w_dev,
+                    int64_t* n_outside, gg_stream stream);
+/* The n order^d entries of W: entry e = i order^d + c of point i (digit f of c
+ * in base `order`, axis 0 lowest, is the offset along axis f) gets its node
+ * (int64) and its weight product.  Sorted stably by node they are the
+ * inverted index of gg_ski_create (the sort is the caller's).               */
+int gg_ski_expand(int d, const int64_t* m, int order, int64_t n, const int32_t* first_dev,
+                  const double* w_dev, int64_t* node_dev, double* wprod_dev, gg_stream stream);
+/* The interpolation operator: the stencil tables and the inverted index of
+ * W^T -- rowptr_dev (N + 1 int64), and per entry in node order (within a node
+ * in point order) the point (int32) and the weight product.  The handle keeps
+ * every pointer (the caller keeps the buffers alive).  Rows of more than
+ * `split` entries are the long rows: long_node_dev (nlong int64, ascending)
+ * names them, row l is cut into the chunks chunk_off_dev[l] ..
+ * chunk_off_dev[l + 1] (nlong + 1 int64), chunk c covers the entries
+ * chunk_begin_dev[c] .. chunk_end_dev[c], and chunk_sum_dev holds nchunks
+ * doubles of scratch.  nlong == 0: the five pointers may be NULL.
+ * gg_ski_spread writes that scratch: a handle with long rows serves one
+ * spread at a time (one stream); it is not safe for concurrent use.  N must
+ * fit an int64 (GG_ERR_VALUE otherwise).                                     */
+typedef struct gg_ski gg_ski;
+int gg_ski_create(int d, const int64_t* m, int order, int64_t n, const int32_t* first_dev,
+                  const double* w_dev, const int64_t* rowptr_dev, const int32_t* point_dev,
+                  const double* wprod_dev, int64_t split, int64_t nlong,
+                  const int64_t* long_node_dev, const int64_t* chunk_off_dev, int64_t nchunks,
+                  const int64_t* chunk_begin_dev, const int64_t* chunk_end_dev,
+                  double* chunk_sum_dev, gg_ski** out);
+int gg_ski_destroy(gg_ski* ski);
+/* t = W g (n doubles from N): the weights are formed on the fly from the
+ * per-axis tables.  Any 8-byte aligned address.                              */
+int gg_ski_interp(const gg_ski* ski, const double* g_dev, double* t_dev, gg_stream stream);
+/* g = W^T p (N doubles from n) without atomics: every node is written exactly
+ * once, an empty row as 0 (no zeroing pass), the sum of a row in a fixed
+ * order -- bitwise reproducible from run to run.  Any 8-byte aligned address. */
+int gg_ski_spread(const gg_ski* ski, const double* p_dev, double* g_dev, gg_stream stream);
+
+/* CG on (W K W^T + shift I) x = b over the n points, x0 = 0: the contracts of
+ * gg_cgm_* (textbook recurrence, device scalars, tolerance max(atol, rtol |b|)
+ * on the recurrence residual, a started handle may be started again with the
+ * same bits).  One iteration: direction, spread, the Kronecker matvec (grid
+ * basis, shift 0), interp with + shift p and the partials of p.A p, alpha, the
+ * x / r update, rho / beta / stopping test.  alpha_j and beta_j of the first
+ * max_steps iterations of a solve are kept on the device
+ * (gg_skicg_coefficients).  work_dev: gg_skicg_work_elems doubles.  x_dev must
+ * be 16-byte aligned, b_dev 8-byte.  GG_ERR_VALUE: a NULL argument, shift <= 0,
+ * max_steps < 0, an operator whose order is not the grid's N.                */
+typedef struct gg_skicg gg_skicg;
+int gg_skicg_work_elems(const gg_kron* K, const gg_ski* ski, int64_t* elems);
+int gg_skicg_create(const gg_kron* K, const gg_ski* ski, double shift, double* work_dev,
+                    int max_steps, gg_skicg** out);
+int gg_skicg_destroy(gg_skicg* cg);
+int gg_skicg_start(gg_skicg* cg, const double* b_dev, double* x_dev, double rtol, double atol,
+                   gg_stream stream);
+int gg_skicg_iterate(gg_skicg* cg, int max_iters, int check_every, gg_stream stream);
+int gg_skicg_status(gg_skicg* cg, int* iters, int* converged, double* resid_norm, double* tol,
+                    gg_stream stream); /* synchronising */
+/* The first min(k, iterations run, max_steps) pairs (alpha_j, beta_j) of the
+ * current solve to host memory, their number to *k_out.  Synchronising.     */
+int gg_skicg_coefficients(gg_skicg* cg, int k, double* alphas, double* betas, int* k_out,
+                          gg_stream stream);
+
 /* ----------------------------------------------- Lanczos (SLQ log-det, P1)
  * k steps of three-term Lanczos on (K + shift I) from z / ||z|| where z is the
  * Rademacher probe (seed, probe) (oracle/cg.py probe_signs).  Writes the
